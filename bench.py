@@ -9,7 +9,9 @@ fixed).  Synthetic 28x28x1 data, random-init weights (the reference's MNIST
 image blobs are absent and the baseline is defined on synthetic data).
 Timing: W untimed warmup steps, then exactly K steps bracketed by
 barrier + torch.cuda.synchronize on both sides; MAX time over ranks;
-rank 0 prints one JSON line.
+rank 0 prints one JSON line.  --dump-outputs DIR then writes the state
+those W + K steps produced; --full repeats the K-step block for short
+runs and reports the median block.
 
 Reference headline being compared against: the CUDA variant's
 2,996.99 ms / 60k-sample epoch on a T4 ~= 20,020 images/sec.
@@ -23,6 +25,37 @@ import time
 import torch
 
 BASELINE_IMAGES_PER_SEC = 60000.0 / 2.9969857  # BASELINE.md CUDA headline
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir: str, trainer) -> None:
+    """Write what the timed path left for its caller after its last step
+    as float32 <name>.npy files: the updated flat parameter vector, the
+    last batch's network outputs, and the running loss sum.  Inputs and
+    initial weights are seeded, so the same arguments give the same
+    trajectory and two builds can be compared array for array."""
+    import os
+
+    import numpy as np
+
+    if trainer.device.type == "cuda":
+        torch.cuda.synchronize()
+    arrays = {"params": trainer.model.params}
+    if trainer.backend == "hip":
+        arrays["loss_accum"] = trainer.ws.loss_accum
+    else:
+        arrays["loss_accum"] = torch.tensor([trainer._loss_host])
+    if trainer.backend != "torchref":  # the oracle path never fills ws.y
+        arrays["y"] = trainer.ws.y
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BUDGET_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if a.nbytes > budget:  # fixed, seeded sample of a larger output
+            idx = np.random.default_rng(0).choice(
+                a.size, budget // 4, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main() -> int:
@@ -53,6 +86,12 @@ def main() -> int:
                         "of remaining wgrad cannot hide — ONE fused bucket "
                         "is the design point (SURVEY 5.8); measure with "
                         "--overlap-comm on multi-GPU nodes")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step "
+                        "left behind (params, y, loss) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline "
+                        "figure: repeated K-step blocks, median reported")
     args = p.parse_args()
 
     from parallel_cnn_amd.config import TrainConfig
@@ -123,12 +162,16 @@ def main() -> int:
             el, device=device if device == "cuda" else None)
 
     run(args.warmup)
-    # Short driver runs (e.g. --steps 20 ~ 0.4 ms timed region) are noise-
+    # A plain run times ONE block of exactly K steps, so warmup + K is the
+    # whole trajectory and the dumped outputs are reproducible.
+    blocks = [timed_block()]
+    if args.dump_outputs and ctx.is_main:
+        dump_outputs(args.dump_outputs, trainer)
+    # --full: short runs (e.g. --steps 20 ~ 0.4 ms timed region) are noise-
     # limited: repeat the K-step block until >= 50 ms of cumulative timed
     # region (each block still times EXACTLY K steps) and report the
     # median block.
-    blocks = [timed_block()]
-    while sum(blocks) < 0.050 and len(blocks) < 64:
+    while args.full and sum(blocks) < 0.050 and len(blocks) < 64:
         blocks.append(timed_block())
     blocks.sort()
     elapsed = blocks[len(blocks) // 2]  # median block

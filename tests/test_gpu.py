@@ -402,11 +402,18 @@ def test_native_cli_trainer(device, tmp_path):
     assert torch.isfinite(m.params).all()
 
 
-def test_bench_contract_single_gpu(device):
+def test_bench_contract_single_gpu(device, tmp_path):
+    import numpy as np
     out = subprocess.run(
         [sys.executable, "bench.py", "--gpus", "1", "--steps", "30",
-         "--warmup", "5"],
+         "--warmup", "5", "--dump-outputs", str(tmp_path)],
         capture_output=True, text=True, timeout=600, check=True)
+    dumped = {f.stem: np.load(f) for f in tmp_path.glob("*.npy")}
+    assert set(dumped) == {"params", "y", "loss_accum"}
+    assert dumped["params"].shape == (S.N_PARAMS,)
+    assert dumped["y"].shape == (64, 10)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all()
+               for a in dumped.values())
     line = [l for l in out.stdout.strip().splitlines() if l.startswith("{")][-1]
     r = json.loads(line)
     assert r["n_gpus"] == 1 and r["steps"] == 30

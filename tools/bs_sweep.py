@@ -1,7 +1,7 @@
 import json, subprocess, sys
 for b in (64, 256, 1024, 4096, 16384, 65536):
     out = subprocess.run([sys.executable, "bench.py", "--gpus", "1",
-                          "--steps", "50", "--warmup", "10",
+                          "--steps", "50", "--warmup", "10", "--full",
                           "--batch-size", str(b)],
                          capture_output=True, text=True, timeout=600)
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
