@@ -45,6 +45,11 @@ int pcnn_launch_wgrad_ex(const void* x, const void* a1, const void* a2,
                          float* grads, int B, int act_is_bf16, int chunk_imgs,
                          int roles, void* stream);
 int pcnn_launch_update(float* params, float* grads, float step, void* stream);
+int pcnn_launch_wgrad_update(const void* x, const void* a1, const void* a2,
+                             const float* dz, const float* dz2,
+                             const void* dz1, float* grads, float* params,
+                             float step, int* ticket, int B, int act_is_bf16,
+                             int chunk_imgs, int roles, void* stream);
 const char* pcnn_hip_error_string(int err);
 // deep (general conv) kernels — csrc/hip/conv_kernels.hip
 int pcnn_deep_im2col(const void* x, void* cols, int B, int H, int W, int Cin,
@@ -203,18 +208,54 @@ void hip_update(at::Tensor params, at::Tensor grads, double step,
             "update");
 }
 
+int* ticket_ptr(const at::Tensor& ticket) {
+  TORCH_CHECK(ticket.is_cuda() && ticket.scalar_type() == at::kInt &&
+                  ticket.numel() >= 1,
+              "ticket must be a device int32 tensor");
+  return ticket.data_ptr<int>();
+}
+
+// Weight gradients with the SGD update as the tail of the same launch:
+// the last block to arrive on `ticket` applies p += step*g and zeroes g.
+void hip_wgrad_update(at::Tensor x, at::Tensor a1, at::Tensor a2,
+                      at::Tensor dz, at::Tensor dz2, at::Tensor dz1,
+                      at::Tensor grads, at::Tensor params, double step,
+                      at::Tensor ticket, int64_t B, int64_t chunk_imgs,
+                      int64_t roles, int64_t stream) {
+  int f = act_flag(x);
+  TORCH_CHECK(dz1.scalar_type() == x.scalar_type(),
+              "dz1 must match the activation dtype");
+  TORCH_CHECK(params.is_cuda() && grads.is_cuda() &&
+                  params.numel() == pcnn::N_PARAMS &&
+                  grads.numel() == pcnn::N_PARAMS,
+              "params/grads must be the flat device buckets");
+  check_hip(pcnn_launch_wgrad_update(
+                x.data_ptr(), a1.data_ptr(), a2.data_ptr(),
+                dz.data_ptr<float>(), dz2.data_ptr<float>(), dz1.data_ptr(),
+                grads.data_ptr<float>(), params.data_ptr<float>(),
+                (float)step, ticket_ptr(ticket), (int)B, f, (int)chunk_imgs,
+                (int)roles, (void*)stream),
+            "wgrad_update");
+}
+
 // Single-GPU fused training loop: enqueues `steps` full training steps
-// (fwd+bwd-data -> wgrad -> update) from C++, cycling a device-resident
-// batch pool.  Asynchronous — caller syncs the stream.  The distributed
-// path keeps the per-step Python loop (the all-reduce sits between wgrad
-// and update there).
+// from C++, cycling a device-resident batch pool.  step_mode 3 is
+// fwd+bwd-data -> wgrad -> update; step_mode 2 is fwd+bwd-data ->
+// wgrad+update (needs `ticket`).  Asynchronous — caller syncs the stream.
+// The distributed path keeps the per-step Python loop (the all-reduce sits
+// between wgrad and update there).
 void hip_train_steps(at::Tensor x_pool, at::Tensor labels_pool,
                      at::Tensor params, at::Tensor grads, at::Tensor a1,
                      at::Tensor a2, at::Tensor y, at::Tensor dz,
                      at::Tensor dz2, at::Tensor dz1, at::Tensor loss_accum,
                      int64_t B, int64_t steps, int64_t chunk_imgs,
                      double step_scale, int64_t stream, int64_t pool_mode,
-                     int64_t loss_mode, int64_t wgrad_fuse) {
+                     int64_t loss_mode, int64_t wgrad_fuse,
+                     int64_t step_mode, at::Tensor ticket) {
+  TORCH_CHECK(step_mode == 3 || step_mode == 2, "step_mode must be 3 or 2");
+  TORCH_CHECK(step_mode == 3 || !wgrad_fuse,
+              "the two-launch step excludes wgrad_fuse");
+  int* tk = step_mode == 2 ? ticket_ptr(ticket) : nullptr;
   // wgrad_fuse=1: conv/pool grads accumulate inside the fwdbwd kernel and
   // kernel B covers only the fc role.  Measured slower at bs=64 (the LDS
   // atomic combine serializes) — default off.
@@ -244,6 +285,15 @@ void hip_train_steps(at::Tensor x_pool, at::Tensor labels_pool,
                                      (int)B, f, 0, (int)pool_mode,
                                      (int)loss_mode, gp, (int)wgrad_fuse, s),
               "train_steps/fwdbwd");
+    if (tk != nullptr) {
+      check_hip(pcnn_launch_wgrad_update(
+                    xb, a1.data_ptr(), a2.data_ptr(), dz.data_ptr<float>(),
+                    dz2.data_ptr<float>(), dz1.data_ptr(), gp, pp,
+                    (float)step_scale, tk, (int)B, f, (int)chunk_imgs, wroles,
+                    s),
+                "train_steps/wgrad_update");
+      continue;
+    }
     check_hip(pcnn_launch_wgrad_ex(xb, a1.data_ptr(), a2.data_ptr(),
                                    dz.data_ptr<float>(), dz2.data_ptr<float>(),
                                    dz1.data_ptr(), gp, (int)B, f,
@@ -578,7 +628,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dz2"), py::arg("dz1"), py::arg("loss_accum"), py::arg("B"),
         py::arg("steps"), py::arg("chunk_imgs"), py::arg("step_scale"),
         py::arg("stream"), py::arg("pool_mode") = 0,
-        py::arg("loss_mode") = 0, py::arg("wgrad_fuse") = 0);
+        py::arg("loss_mode") = 0, py::arg("wgrad_fuse") = 0,
+        py::arg("step_mode") = 3, py::arg("ticket") = at::empty({0}));
+  m.def("hip_wgrad_update", &hip_wgrad_update, py::arg("x"), py::arg("a1"),
+        py::arg("a2"), py::arg("dz"), py::arg("dz2"), py::arg("dz1"),
+        py::arg("grads"), py::arg("params"), py::arg("step"),
+        py::arg("ticket"), py::arg("B"), py::arg("chunk_imgs"),
+        py::arg("roles"), py::arg("stream"));
   m.def("deep_im2col", &deep_im2col);
   m.def("deep_gemm", &deep_gemm, py::arg("A"), py::arg("Bsrc"),
         py::arg("bias"), py::arg("C"), py::arg("M"), py::arg("K"),

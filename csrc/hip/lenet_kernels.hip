@@ -24,6 +24,14 @@
 //      (k,m) pairs — no atomics, plain accumulate-stores.
 //   3. k_update  — SGD apply (p += dt*scale*g) fused with gradient zeroing.
 //
+// On one GPU with nothing between weight-grad and update (no all-reduce,
+// no gradient accumulation) the step is TWO kernels: k_wgrad_update is
+// k_wgrad with the update as its tail.  Every block arrives once on a
+// device ticket and exits; the block that arrives last applies the update
+// and zeroes the bucket.  Nothing waits on anything, so there is no grid
+// barrier and no spin (a grid barrier costs more than the kernel boundary
+// it would replace).
+//
 // Numerics: activations AND the large conv preact gradient (dz1) are
 // stored bf16/fp16/fp32 (template); ALL arithmetic is fp32 in
 // registers/LDS; parameters, gradients, dz and dz2 are fp32.  Loss-metric
@@ -403,8 +411,17 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-template <typename act_t>
-__global__ __launch_bounds__(256) void k_wgrad(
+// The whole role dispatch lives in one device function so that the plain
+// kernel and the update-fused kernel below run the very same gradient code.
+// A masked-off role returns from this function only, never from the kernel.
+//
+// WT (update-fused kernel only): the fc role's owner stores are agent-scope
+// write-through stores instead of plain ones, so that — like the conv and
+// pool roles' hardware atomics — they have left this XCD's L2 once the
+// storing wave's vmcnt has drained, and the hand-off to the block that
+// applies the update needs no L2 write-back.
+template <typename act_t, bool WT>
+__device__ __forceinline__ void wgrad_body(
     const act_t* __restrict__ x, const act_t* __restrict__ a1g,
     const act_t* __restrict__ a2g, const float* __restrict__ dzg,
     const float* __restrict__ dz2g, const act_t* __restrict__ dz1g,
@@ -586,7 +603,10 @@ __global__ __launch_bounds__(256) void k_wgrad(
 #pragma unroll 8
       for (int b = b_lo; b < b_hi; ++b)
         acc += dzg[(size_t)b * FC_OUT + k] * ldf(a2g + (size_t)b * FC_IN + m);
-      if (FS == 1)
+      if (FS == 1 && WT)
+        __hip_atomic_store(&grads[OFF_FW + q], grads[OFF_FW + q] + acc,
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else if (FS == 1)
         grads[OFF_FW + q] += acc;
       else
         unsafeAtomicAdd(&grads[OFF_FW + q], acc);
@@ -595,12 +615,105 @@ __global__ __launch_bounds__(256) void k_wgrad(
       float acc = 0.f;
 #pragma unroll 8
       for (int b = b_lo; b < b_hi; ++b) acc += dzg[(size_t)b * FC_OUT + k];
-      if (FS == 1)
+      if (FS == 1 && WT)
+        __hip_atomic_store(&grads[OFF_FB + k], grads[OFF_FB + k] + acc,
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else if (FS == 1)
         grads[OFF_FB + k] += acc;
       else
         unsafeAtomicAdd(&grads[OFF_FB + k], acc);
     }
   }
+}
+
+template <typename act_t>
+__global__ __launch_bounds__(256) void k_wgrad(
+    const act_t* __restrict__ x, const act_t* __restrict__ a1g,
+    const act_t* __restrict__ a2g, const float* __restrict__ dzg,
+    const float* __restrict__ dz2g, const act_t* __restrict__ dz1g,
+    float* __restrict__ grads, int B, int GC, int GS, int FS, int roles) {
+  wgrad_body<act_t, false>(x, a1g, a2g, dzg, dz2g, dz1g, grads, B, GC, GS,
+                           FS, roles);
+}
+
+// ---------------------------------------------------------------------------
+// Arrival ticket: every block of a launch arrives exactly once and exits;
+// nothing waits.  Returns true (block-uniform) in the block that arrived
+// last, after which that block may read everything the other blocks wrote
+// before they arrived.
+//
+// Publish side: everything a block hands over is written with agent-scope
+// atomics or agent-scope write-through stores (never plain stores), so it
+// has left the XCD's L2 once the writing wave's vmcnt has drained; every
+// wave drains, the block meets at a barrier, then one lane draws a ticket
+// with a returning agent-scope atomic.  An agent-scope release fence (an
+// L2 write-back, ~1.7 us in every block) in front of the ticket measured
+// 19.0 us/step against 18.6 for three launches, which is why the payload
+// is write-through instead.  Consume side: the lane that drew gridDim.x-1
+// does an agent-scope acquire and drains it before the barrier that lets
+// the other waves load.  Visibility therefore never depends on which XCD
+// a block ran on.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ bool arrive_is_last(int* __restrict__ ticket) {
+  __shared__ int s_last;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int t = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_AGENT);
+    const int last = (t == (int)gridDim.x - 1);
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    s_last = last;
+  }
+  __syncthreads();
+  return s_last != 0;
+}
+
+// SGD apply + gradient zeroing over the whole bucket by ONE 256-thread
+// block (the last arriver): p += step*g; g = 0.  Same float4 split as
+// k_update: 585 vectors + a 3-float scalar tail.
+__device__ __forceinline__ void update_tail(float* __restrict__ params,
+                                            float* __restrict__ grads,
+                                            float step) {
+  constexpr int NV = N_PARAMS / 4;
+  for (int i4 = threadIdx.x; i4 < NV; i4 += 256) {
+    const int i = i4 * 4;
+    float4 pv = *reinterpret_cast<float4*>(params + i);
+    const float4 gv = *reinterpret_cast<float4*>(grads + i);
+    pv.x += step * gv.x;
+    pv.y += step * gv.y;
+    pv.z += step * gv.z;
+    pv.w += step * gv.w;
+    *reinterpret_cast<float4*>(params + i) = pv;
+    *reinterpret_cast<float4*>(grads + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  const int u = NV * 4 + threadIdx.x;
+  if (u < N_PARAMS) {
+    params[u] += step * grads[u];
+    grads[u] = 0.f;
+  }
+}
+
+// Weight gradients with the SGD update as the tail of the same launch
+// (two-launch training step).  Gradient code is wgrad_body, unchanged; the
+// block that arrives last applies the update, zeroes the bucket and resets
+// the ticket for the next launch.
+template <typename act_t>
+__global__ __launch_bounds__(256) void k_wgrad_update(
+    const act_t* __restrict__ x, const act_t* __restrict__ a1g,
+    const act_t* __restrict__ a2g, const float* __restrict__ dzg,
+    const float* __restrict__ dz2g, const act_t* __restrict__ dz1g,
+    float* __restrict__ grads, int B, int GC, int GS, int FS, int roles,
+    float* __restrict__ params, float step, int* __restrict__ ticket) {
+  wgrad_body<act_t, true>(x, a1g, a2g, dzg, dz2g, dz1g, grads, B, GC, GS,
+                          FS, roles);
+  if (!arrive_is_last(ticket)) return;
+  update_tail(params, grads, step);
+  if (threadIdx.x == 0)
+    __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---------------------------------------------------------------------------
@@ -714,10 +827,14 @@ int pcnn_launch_fwdbwd(const void* x, const float* params, void* a1, void* a2,
 }
 
 // chunk_imgs is the conv1 slices-per-channel knob (GC); <=0 -> default.
-int pcnn_launch_wgrad_ex(const void* x, const void* a1, const void* a2,
-                         const float* dz, const float* dz2, const void* dz1,
-                         float* grads, int B, int act_is_bf16, int chunk_imgs,
-                         int roles, void* stream) {
+// ticket == nullptr launches the plain k_wgrad; otherwise k_wgrad_update
+// with the same grid.
+static int launch_wgrad_any(const void* x, const void* a1, const void* a2,
+                            const float* dz, const float* dz2,
+                            const void* dz1, float* grads, int B,
+                            int act_is_bf16, int chunk_imgs, int roles,
+                            float* params, float step, int* ticket,
+                            void* stream) {
   // Batch-adaptive defaults: ~36 (image,position) items per conv thread,
   // pool slices at GC/4, fc batch slices of ~64 images.
   int GC = chunk_imgs > 0 ? chunk_imgs : (int)(4.0f * __builtin_cbrtf((float)B) + 0.5f);
@@ -735,7 +852,24 @@ int pcnn_launch_wgrad_ex(const void* x, const void* a1, const void* a2,
   if (FS > 32) FS = 32;
   dim3 grid(C1_CH * GC + GS + FS * FC_BLOCKS), block(256);
   hipStream_t s = (hipStream_t)stream;
-  if (act_is_bf16 == 1) {
+  if (ticket != nullptr) {
+    if (act_is_bf16 == 1) {
+      hipLaunchKernelGGL((k_wgrad_update<bf16>), grid, block, 0, s,
+                         (const bf16*)x, (const bf16*)a1, (const bf16*)a2, dz,
+                         dz2, (const bf16*)dz1, grads, B, GC, GS, FS, roles,
+                         params, step, ticket);
+    } else if (act_is_bf16 == 2) {
+      hipLaunchKernelGGL((k_wgrad_update<fp16>), grid, block, 0, s,
+                         (const fp16*)x, (const fp16*)a1, (const fp16*)a2, dz,
+                         dz2, (const fp16*)dz1, grads, B, GC, GS, FS, roles,
+                         params, step, ticket);
+    } else {
+      hipLaunchKernelGGL((k_wgrad_update<float>), grid, block, 0, s,
+                         (const float*)x, (const float*)a1, (const float*)a2,
+                         dz, dz2, (const float*)dz1, grads, B, GC, GS, FS,
+                         roles, params, step, ticket);
+    }
+  } else if (act_is_bf16 == 1) {
     hipLaunchKernelGGL((k_wgrad<bf16>), grid, block, 0, s, (const bf16*)x,
                        (const bf16*)a1, (const bf16*)a2, dz, dz2,
                        (const bf16*)dz1, grads, B, GC, GS, FS, roles);
@@ -749,6 +883,42 @@ int pcnn_launch_wgrad_ex(const void* x, const void* a1, const void* a2,
                        (const float*)dz1, grads, B, GC, GS, FS, roles);
   }
   return (int)hipGetLastError();
+}
+
+int pcnn_launch_wgrad_ex(const void* x, const void* a1, const void* a2,
+                         const float* dz, const float* dz2, const void* dz1,
+                         float* grads, int B, int act_is_bf16, int chunk_imgs,
+                         int roles, void* stream) {
+  return launch_wgrad_any(x, a1, a2, dz, dz2, dz1, grads, B, act_is_bf16,
+                          chunk_imgs, roles, nullptr, 0.f, nullptr, stream);
+}
+
+// Weight gradients + SGD update in one launch (k_wgrad_update).  `ticket`
+// is one device int32 that reads 0 before the launch and 0 again after it.
+int pcnn_launch_wgrad_update(const void* x, const void* a1, const void* a2,
+                             const float* dz, const float* dz2,
+                             const void* dz1, float* grads, float* params,
+                             float step, int* ticket, int B, int act_is_bf16,
+                             int chunk_imgs, int roles, void* stream) {
+  if (ticket == nullptr || params == nullptr) return (int)hipErrorInvalidValue;
+  // Measured crossover (MI355X, us/step, fused vs three launches in one
+  // job): B=16 17.16 vs 17.37, 64 18.45 vs 18.96, 256 23.64 vs 23.88,
+  // 1024 42.31 vs 42.43, 4096 bf16 101.2 vs 100.7, 4096 fp16 101.6 vs
+  // 102.0.  The tail saves a fixed ~0.5 us at best; by B=4096 the
+  // thousands of blocks that each drain and draw a ticket have used it up
+  // and the difference is noise, so large batches keep the kernel boundary.
+  if (B > 2048) {
+    const int err =
+        launch_wgrad_any(x, a1, a2, dz, dz2, dz1, grads, B, act_is_bf16,
+                         chunk_imgs, roles, nullptr, 0.f, nullptr, stream);
+    if (err != 0) return err;
+    dim3 ugrid((N_PARAMS / 4 + 255) / 256), ublock(256);
+    hipLaunchKernelGGL(k_update, ugrid, ublock, 0, (hipStream_t)stream,
+                       params, grads, step);
+    return (int)hipGetLastError();
+  }
+  return launch_wgrad_any(x, a1, a2, dz, dz2, dz1, grads, B, act_is_bf16,
+                          chunk_imgs, roles, params, step, ticket, stream);
 }
 
 int pcnn_launch_wgrad(const void* x, const void* a1, const void* a2,

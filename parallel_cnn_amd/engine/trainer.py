@@ -2,7 +2,10 @@
 Main.cpp `learn()` / `test()` / `classify()`.
 
 Backends:
-  * "hip"      — the gfx950 HIP kernels (3 fused launches per step);
+  * "hip"      — the gfx950 HIP kernels (2 launches per step on one GPU:
+                 fwd+bwd-data, then weight-grad with the SGD update as
+                 its tail; 3 wherever something sits between weight-grad
+                 and update — all-reduce, accumulation, phase timers);
   * "cpu"      — the native C++ reference ops (threaded, race-free);
   * "torchref" — the pure-PyTorch fp32 oracle (tests/debugging).
 
@@ -13,6 +16,7 @@ only synced on readout.
 """
 from __future__ import annotations
 
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -46,6 +50,9 @@ class Workspace:
         self.dz1 = torch.empty(B, S.C1_OUT, dtype=act_dtype, device=dev)
         self.loss_accum = torch.zeros(1, dtype=torch.float32, device=dev)
         self.correct_accum = torch.zeros(1, dtype=torch.int32, device=dev)
+        # arrival ticket of the update-fused weight-grad kernel: reads 0
+        # between launches (the last block to arrive resets it)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
 
 
 class Trainer:
@@ -86,6 +93,24 @@ class Trainer:
         self._fuse = 1 if cfg.fuse_wgrad else 0
         self._wroles = 4 if self._fuse else (5 if self._pool_mode == 1
                                              else 7)
+        # launches per LeNet training step, read once here:
+        # PCNN_LENET_STEP=3 is fwdbwd -> wgrad -> update, 2 (default) runs
+        # the update as the tail of the wgrad launch.
+        mode = os.environ.get("PCNN_LENET_STEP", "2")
+        if mode not in ("2", "3"):
+            raise ValueError(
+                f"PCNN_LENET_STEP must be 3 or 2, got {mode!r}")
+        self._step_mode = int(mode)
+
+    def _fused_step_mode(self) -> int:
+        """2 when the update may run inside the wgrad launch: nothing may
+        sit between weight-grad and update (no all-reduce, no gradient
+        accumulation, no fused-wgrad split, no phase timers)."""
+        if (self._step_mode == 2 and self.backend == "hip"
+                and self.cfg.grad_accum == 1 and not self._fuse
+                and self.timers is None and not pdist.is_distributed()):
+            return 2
+        return 3
 
     # ------------------------------------------------------------------ util
     def _update_scale(self, local_batch: int) -> float:
@@ -135,7 +160,14 @@ class Trainer:
                                w.dz1, labels, w.loss_accum, w.correct_accum,
                                B, MODE_TRAIN, stream, self._pool_mode,
                                self._loss_mode, m.grads, self._fuse)
-            if not apply_update:
+            if self._fused_step_mode() == 2:
+                self._C.hip_wgrad_update(x, w.a1, w.a2, w.dz, w.dz2, w.dz1,
+                                         m.grads, m.params,
+                                         self.cfg.dt * scale, w.ticket, B,
+                                         self.cfg.wgrad_chunk, self._wroles,
+                                         stream)
+                apply_update = False  # done in the wgrad launch
+            elif not apply_update:
                 self._C.hip_wgrad_roles(x, w.a1, w.a2, w.dz, w.dz2, w.dz1,
                                         m.grads, B, self.cfg.wgrad_chunk,
                                         self._wroles, stream)
@@ -235,7 +267,7 @@ class Trainer:
 
     # ------------------------------------------------------------ hipGraph
     def enable_graph(self) -> None:
-        """Capture one full training step (3 kernels + the RCCL all-reduce
+        """Capture one full training step (2 kernels; 3 + the RCCL all-reduce
         when distributed) into a hipGraph; run_steps_pooled then replays it.
         Requires world_size==1 or the nccl/RCCL backend (gloo is host-side,
         not capturable)."""
@@ -276,6 +308,13 @@ class Trainer:
                            w.dz1, self._gl, w.loss_accum, w.correct_accum,
                            B, MODE_TRAIN, stream, self._pool_mode,
                            self._loss_mode, m.grads, self._fuse)
+        if self._fused_step_mode() == 2:
+            self._C.hip_wgrad_update(self._gx, w.a1, w.a2, w.dz, w.dz2,
+                                     w.dz1, m.grads, m.params,
+                                     self.cfg.dt * self._update_scale(B),
+                                     w.ticket, B, self.cfg.wgrad_chunk,
+                                     self._wroles, stream)
+            return
         self._C.hip_wgrad_roles(self._gx, w.a1, w.a2, w.dz, w.dz2, w.dz1,
                                 m.grads, B, self.cfg.wgrad_chunk,
                                 self._wroles, stream)
@@ -312,7 +351,8 @@ class Trainer:
                 w.a1, w.a2, w.y, w.dz, w.dz2, w.dz1, w.loss_accum, B, steps,
                 self.cfg.wgrad_chunk, self.cfg.dt * self._update_scale(B),
                 native.current_stream_handle(), self._pool_mode,
-                self._loss_mode, self._fuse)
+                self._loss_mode, self._fuse, self._fused_step_mode(),
+                w.ticket)
             self._samples_seen += B * steps
             self.global_step += steps
         else:
