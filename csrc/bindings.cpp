@@ -50,6 +50,22 @@ int pcnn_launch_wgrad_update(const void* x, const void* a1, const void* a2,
                              const void* dz1, float* grads, float* params,
                              float step, int* ticket, int B, int act_is_bf16,
                              int chunk_imgs, int roles, void* stream);
+int pcnn_launch_fwdbwd_inblock(const void* x, const float* params, void* a2,
+                               float* y, float* dz, const int* labels,
+                               float* loss_accum, float* gslab, int B,
+                               int act_is_bf16, int pool_mode, int loss_mode,
+                               void* stream);
+int pcnn_launch_reduce_update(const float* gslab, const void* a2,
+                              const float* dz, float* params, float step,
+                              int B, int act_is_bf16, void* stream);
+int pcnn_inblock_max_batch();
+int pcnn_launch_step_inblock(const void* x, float* params, void* a1, void* a2,
+                             float* y, float* dz, float* dz2, void* dz1,
+                             const int* labels, float* loss_accum,
+                             float* grads, int* ticket, float* gslab,
+                             float step, int B, int act_is_bf16,
+                             int pool_mode, int loss_mode, int chunk_imgs,
+                             void* stream);
 const char* pcnn_hip_error_string(int err);
 // deep (general conv) kernels — csrc/hip/conv_kernels.hip
 int pcnn_deep_im2col(const void* x, void* cols, int B, int H, int W, int Cin,
@@ -238,10 +254,86 @@ void hip_wgrad_update(at::Tensor x, at::Tensor a1, at::Tensor a2,
             "wgrad_update");
 }
 
+float* gslab_ptr(const at::Tensor& gslab, int64_t B) {
+  TORCH_CHECK(gslab.is_cuda() && gslab.scalar_type() == at::kFloat &&
+                  gslab.is_contiguous() &&
+                  gslab.numel() >= B * pcnn::GSLAB_LD,
+              "gslab must be a contiguous device fp32 [>=B, ",
+              pcnn::GSLAB_LD, "] tensor");
+  return gslab.data_ptr<float>();
+}
+
+// First kernel of the in-block weight-grad step on its own: forward +
+// backward-data in train mode, with this batch's conv/pool gradient sums
+// written to rows [0, B) of gslab.  a1, dz1 and dz2 are not produced.
+void hip_fwdbwd_inblock(at::Tensor x, at::Tensor params, at::Tensor a2,
+                        at::Tensor y, at::Tensor dz, at::Tensor labels,
+                        at::Tensor loss_accum, at::Tensor gslab, int64_t B,
+                        int64_t stream, int64_t pool_mode,
+                        int64_t loss_mode) {
+  TORCH_CHECK(x.is_cuda() && params.is_cuda(), "expected device tensors");
+  TORCH_CHECK(labels.scalar_type() == at::kInt, "labels must be int32");
+  TORCH_CHECK(B >= 1 && x.numel() >= B * pcnn::IN_PIX &&
+                  a2.numel() >= B * pcnn::S1_OUT &&
+                  a2.scalar_type() == x.scalar_type() &&
+                  y.numel() >= B * pcnn::FC_OUT &&
+                  dz.numel() >= B * pcnn::FC_OUT && labels.numel() >= B,
+              "buffers too small for B");
+  check_hip(pcnn_launch_fwdbwd_inblock(
+                x.data_ptr(), params.data_ptr<float>(), a2.data_ptr(),
+                y.data_ptr<float>(), dz.data_ptr<float>(),
+                labels.data_ptr<int>(),
+                loss_accum.numel() ? loss_accum.data_ptr<float>() : nullptr,
+                gslab_ptr(gslab, B), (int)B, act_flag(x), (int)pool_mode,
+                (int)loss_mode, (void*)stream),
+            "fwdbwd_inblock");
+}
+
+// One whole training step with in-block weight grads (k_fwdbwd<INBLOCK> ->
+// k_reduce_update); above _C.INBLOCK_MAX_BATCH the launcher runs
+// k_fwdbwd -> k_wgrad_update instead, which is why it takes every buffer.
+void hip_step_inblock(at::Tensor x, at::Tensor params, at::Tensor a1,
+                      at::Tensor a2, at::Tensor y, at::Tensor dz,
+                      at::Tensor dz2, at::Tensor dz1, at::Tensor labels,
+                      at::Tensor loss_accum, at::Tensor grads,
+                      at::Tensor ticket, at::Tensor gslab, double step,
+                      int64_t B, int64_t chunk_imgs, int64_t stream,
+                      int64_t pool_mode, int64_t loss_mode) {
+  TORCH_CHECK(x.is_cuda() && params.is_cuda(), "expected device tensors");
+  TORCH_CHECK(labels.scalar_type() == at::kInt, "labels must be int32");
+  TORCH_CHECK(dz1.scalar_type() == x.scalar_type() &&
+                  a2.scalar_type() == x.scalar_type(),
+              "a2/dz1 must match the activation dtype");
+  TORCH_CHECK(params.numel() == pcnn::N_PARAMS &&
+                  grads.numel() == pcnn::N_PARAMS,
+              "params/grads must be the flat device buckets");
+  TORCH_CHECK(B >= 1 && x.numel() >= B * pcnn::IN_PIX &&
+                  a2.numel() >= B * pcnn::S1_OUT &&
+                  y.numel() >= B * pcnn::FC_OUT &&
+                  dz.numel() >= B * pcnn::FC_OUT && labels.numel() >= B,
+              "buffers too small for B");
+  TORCH_CHECK(B <= pcnn_inblock_max_batch() ||
+                  (a1.numel() >= B * pcnn::C1_OUT &&
+                   dz1.numel() >= B * pcnn::C1_OUT &&
+                   dz2.numel() >= B * pcnn::S1_OUT),
+              "a1/dz1/dz2 too small for the large-batch path");
+  check_hip(pcnn_launch_step_inblock(
+                x.data_ptr(), params.data_ptr<float>(), a1.data_ptr(),
+                a2.data_ptr(), y.data_ptr<float>(), dz.data_ptr<float>(),
+                dz2.data_ptr<float>(), dz1.data_ptr(), labels.data_ptr<int>(),
+                loss_accum.data_ptr<float>(), grads.data_ptr<float>(),
+                ticket_ptr(ticket), gslab_ptr(gslab, B), (float)step, (int)B,
+                act_flag(x), (int)pool_mode, (int)loss_mode, (int)chunk_imgs,
+                (void*)stream),
+            "step_inblock");
+}
+
 // Single-GPU fused training loop: enqueues `steps` full training steps
 // from C++, cycling a device-resident batch pool.  step_mode 3 is
 // fwd+bwd-data -> wgrad -> update; step_mode 2 is fwd+bwd-data ->
-// wgrad+update (needs `ticket`).  Asynchronous — caller syncs the stream.
+// wgrad+update (needs `ticket`); step_mode 4 is the in-block weight-grad
+// step, fwd+bwd-data+conv/pool grads -> reduce+update (needs `ticket` and
+// `gslab`).  Asynchronous — caller syncs the stream.
 // The distributed path keeps the per-step Python loop (the all-reduce sits
 // between wgrad and update there).
 void hip_train_steps(at::Tensor x_pool, at::Tensor labels_pool,
@@ -251,11 +343,14 @@ void hip_train_steps(at::Tensor x_pool, at::Tensor labels_pool,
                      int64_t B, int64_t steps, int64_t chunk_imgs,
                      double step_scale, int64_t stream, int64_t pool_mode,
                      int64_t loss_mode, int64_t wgrad_fuse,
-                     int64_t step_mode, at::Tensor ticket) {
-  TORCH_CHECK(step_mode == 3 || step_mode == 2, "step_mode must be 3 or 2");
+                     int64_t step_mode, at::Tensor ticket,
+                     at::Tensor gslab) {
+  TORCH_CHECK(step_mode == 3 || step_mode == 2 || step_mode == 4,
+              "step_mode must be 3, 2 or 4");
   TORCH_CHECK(step_mode == 3 || !wgrad_fuse,
-              "the two-launch step excludes wgrad_fuse");
-  int* tk = step_mode == 2 ? ticket_ptr(ticket) : nullptr;
+              "the two-launch steps exclude wgrad_fuse");
+  int* tk = step_mode != 3 ? ticket_ptr(ticket) : nullptr;
+  float* slab = step_mode == 4 ? gslab_ptr(gslab, B) : nullptr;
   // wgrad_fuse=1: conv/pool grads accumulate inside the fwdbwd kernel and
   // kernel B covers only the fc role.  Measured slower at bs=64 (the LDS
   // atomic combine serializes) — default off.
@@ -276,6 +371,16 @@ void hip_train_steps(at::Tensor x_pool, at::Tensor labels_pool,
     const int64_t i = st % P;
     const void* xb = xp + (size_t)i * B * pcnn::IN_PIX * esz;
     const int* lb = lp + i * B;
+    if (slab != nullptr) {
+      check_hip(pcnn_launch_step_inblock(
+                    xb, pp, a1.data_ptr(), a2.data_ptr(), y.data_ptr<float>(),
+                    dz.data_ptr<float>(), dz2.data_ptr<float>(),
+                    dz1.data_ptr(), lb, loss_accum.data_ptr<float>(), gp, tk,
+                    slab, (float)step_scale, (int)B, f, (int)pool_mode,
+                    (int)loss_mode, (int)chunk_imgs, s),
+                "train_steps/step_inblock");
+      continue;
+    }
     check_hip(pcnn_launch_fwdbwd_ex2(xb, pp, a1.data_ptr(), a2.data_ptr(),
                                      y.data_ptr<float>(),
                                      dz.data_ptr<float>(),
@@ -629,7 +734,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("steps"), py::arg("chunk_imgs"), py::arg("step_scale"),
         py::arg("stream"), py::arg("pool_mode") = 0,
         py::arg("loss_mode") = 0, py::arg("wgrad_fuse") = 0,
-        py::arg("step_mode") = 3, py::arg("ticket") = at::empty({0}));
+        py::arg("step_mode") = 3, py::arg("ticket") = at::empty({0}),
+        py::arg("gslab") = at::empty({0}));
+  m.def("hip_fwdbwd_inblock", &hip_fwdbwd_inblock, py::arg("x"),
+        py::arg("params"), py::arg("a2"), py::arg("y"), py::arg("dz"),
+        py::arg("labels"), py::arg("loss_accum"), py::arg("gslab"),
+        py::arg("B"), py::arg("stream"), py::arg("pool_mode") = 0,
+        py::arg("loss_mode") = 0);
+  m.def("hip_step_inblock", &hip_step_inblock, py::arg("x"),
+        py::arg("params"), py::arg("a1"), py::arg("a2"), py::arg("y"),
+        py::arg("dz"), py::arg("dz2"), py::arg("dz1"), py::arg("labels"),
+        py::arg("loss_accum"), py::arg("grads"), py::arg("ticket"),
+        py::arg("gslab"), py::arg("step"), py::arg("B"),
+        py::arg("chunk_imgs"), py::arg("stream"), py::arg("pool_mode") = 0,
+        py::arg("loss_mode") = 0);
   m.def("hip_wgrad_update", &hip_wgrad_update, py::arg("x"), py::arg("a1"),
         py::arg("a2"), py::arg("dz"), py::arg("dz2"), py::arg("dz1"),
         py::arg("grads"), py::arg("params"), py::arg("step"),
@@ -675,6 +793,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("deep_update", &deep_update);
   m.def("deep_mfma_selftest", &deep_mfma_selftest);
   m.attr("N_PARAMS") = pcnn::N_PARAMS;
+  m.attr("GSLAB_LD") = pcnn::GSLAB_LD;
+  m.attr("INBLOCK_MAX_BATCH") = pcnn_inblock_max_batch();
   m.attr("OFF_C1W") = pcnn::OFF_C1W;
   m.attr("OFF_C1B") = pcnn::OFF_C1B;
   m.attr("OFF_S1W") = pcnn::OFF_S1W;

@@ -32,6 +32,21 @@
 // barrier and no spin (a grid barrier costs more than the kernel boundary
 // it would replace).
 //
+// In-block weight grads (PCNN_LENET_WGRAD=inblock) are a different two-kernel
+// step for the same case.  k_wgrad_update exists only to redo, from global
+// memory, a reduction over values k_fwdbwd already held in registers, and
+// its critical path is four or five serial fabric round trips.  Instead:
+//
+//   1. k_fwdbwd<.., INBLOCK> — as above, but each cell thread also forms its
+//      conv (25 + bias) and pool (16 + bias) gradient partials from dz1, a1
+//      and the input window in registers; one LDS hop with a fixed-order sum
+//      gives the image's 173 conv/pool sums, stored as one row of a
+//      [B][176] fp32 slab.  a1, dz1 and dz2 are never stored.
+//   2. k_reduce_update — one owner group of 4 lanes per parameter: sums the
+//      slab column or the fc outer product over the batch and applies the
+//      SGD update.  No atomics, no gradient bucket, no ticket, no fences;
+//      results are bit-reproducible.
+//
 // Numerics: activations AND the large conv preact gradient (dz1) are
 // stored bf16/fp16/fp32 (template); ALL arithmetic is fp32 in
 // registers/LDS; parameters, gradients, dz and dz2 are fp32.  Loss-metric
@@ -127,6 +142,23 @@ struct FwdLds {
   float gs1[S1_WSZ + 1];
 };
 
+// In-block weight-grad step (slab layout: GSLAB_LD in lenet_dims.h).
+// LDS rows of per-thread partials: 26 conv (25 weights + bias sum) then 17
+// pool (16 weights + bias sum); odd stride -> conflict-free row writes.
+constexpr int IB_CONV = C1_K * C1_K + 1;        // 26
+constexpr int IB_LD = IB_CONV + S1_WSZ + 1;     // 43
+constexpr int IB_POOL_T0 = 160;  // first pool-owner thread (4-lane aligned)
+static_assert(IB_LD % 2 == 1, "odd LDS row stride");
+static_assert(C1_CH * IB_CONV <= IB_POOL_T0 &&
+                  IB_POOL_T0 + 4 * (S1_WSZ + 1) <= 256 && S1_OUT % 8 == 0 &&
+                  S1_PIX % 4 == 0 && OFF_FW <= GSLAB_LD,
+              "owner layout");
+// One function-local __shared__ array, only present in kernels that call it.
+__device__ __forceinline__ float* inblock_rows() {
+  __shared__ float rows[S1_OUT * IB_LD];
+  return rows;
+}
+
 // Fused forward + backward-data, one 256-thread workgroup per image.
 //
 // Dataflow: thread t < 216 OWNS pool cell (o, pr, pc) — it computes the
@@ -136,7 +168,14 @@ struct FwdLds {
 // That ownership removes the conv->pool and fc-bwd->pool-bwd barriers and
 // all cross-thread a1 LDS traffic: the kernel has 3 barriers total
 // ({stage} {conv+pool} {fc+residual} {fc-bwd + pool-bwd + loss}).
-template <typename act_t, int MODE>
+//
+// INBLOCK (MODE_TRAIN only) is the first kernel of the in-block weight-grad
+// step: the conv and pool weight gradients of this image are formed from
+// the registers that already hold dz1, a1 and the input window, reduced
+// over the block through LDS in a fixed order, and stored as row b of the
+// slab that `grads` points to in this variant (see GSLAB_LD).  a1, dz1 and
+// dz2 are then not stored at all, because nothing reads them.
+template <typename act_t, int MODE, bool INBLOCK = false>
 __global__ __launch_bounds__(256) void k_fwdbwd(
     const act_t* __restrict__ x, const float* __restrict__ params,
     act_t* __restrict__ a1g, act_t* __restrict__ a2g, float* __restrict__ yg,
@@ -169,9 +208,9 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
   const int pc = pq - pr * S1_W;
   float a1v[S1_K * S1_K];  // this cell's conv activations, kept live to bwd
   float a2v = 0.f;
+  float xw[8][8];  // this cell's input window; INBLOCK keeps it live to bwd
   if (tid < S1_OUT) {
     // load the cell's 8x8 input window into registers (2 x 8B loads/row)
-    float xw[8][8];
 #pragma unroll
     for (int u = 0; u < 8; ++u)
 #pragma unroll
@@ -200,7 +239,7 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
           pacc += params[OFF_S1W + i * S1_K + j] * av;
       }
     }
-    if (MODE == MODE_TRAIN) {
+    if (MODE == MODE_TRAIN && !INBLOCK) {
       // 4-wide activation stores per conv row
 #pragma unroll
       for (int i = 0; i < S1_K; ++i)
@@ -297,7 +336,7 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
     for (int k = 0; k < FC_OUT; ++k)
       da += params[OFF_FW + k * FC_IN + tid] * L.dzs[k];
     const float d2 = da * a2v * (1.0f - a2v);
-    dz2g[(size_t)b * S1_OUT + tid] = d2;
+    if (!INBLOCK) dz2g[(size_t)b * S1_OUT + tid] = d2;
     // pool backward for this thread's own 16 conv positions (registers):
     // trainable -> d2 * kernel weight everywhere; max -> d2 at the argmax
     int best = 0;
@@ -322,11 +361,47 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
                 : d2 * params[OFF_S1W + i * S1_K + j];
         dz1v[i * S1_K + j] = dd * av * (1.0f - av);
       }
-      st4f(dz1g + (size_t)b * C1_OUT + o * C1_PIX + (pr * S1_K + i) * C1_W +
-               pc * S1_K,
-           &dz1v[i * S1_K]);
+      if (!INBLOCK)
+        st4f(dz1g + (size_t)b * C1_OUT + o * C1_PIX +
+                 (pr * S1_K + i) * C1_W + pc * S1_K,
+             &dz1v[i * S1_K]);
     }
-    if (wgrad_fuse) {
+    if constexpr (INBLOCK) {
+      // conv1 partial of this cell: 16 dz1 x the 8x8 window, all registers
+      // (400 FMAs, no loads); pool partial: d2 x the cell's 16 activations.
+      // dz1 and a1 enter rounded to the activation dtype, which is what the
+      // k_wgrad path reads back from memory, so both paths form the same
+      // products and differ only in summation order.  That is a choice made
+      // so the two paths stay comparable (same-results table, profiles/r4),
+      // not a requirement: the unrounded registers would be more accurate
+      // and save 32 conversions per thread.
+      float cacc[C1_K * C1_K];
+#pragma unroll
+      for (int w2 = 0; w2 < C1_K * C1_K; ++w2) cacc[w2] = 0.f;
+      float csum = 0.f;
+#pragma unroll
+      for (int i = 0; i < S1_K; ++i)
+#pragma unroll
+        for (int j = 0; j < S1_K; ++j) {
+          const float d = (float)(act_t)dz1v[i * S1_K + j];
+          csum += d;
+#pragma unroll
+          for (int u = 0; u < C1_K; ++u)
+#pragma unroll
+            for (int v = 0; v < C1_K; ++v)
+              cacc[u * C1_K + v] += d * xw[i + u][j + v];
+        }
+      float* row = inblock_rows() + tid * IB_LD;
+#pragma unroll
+      for (int w2 = 0; w2 < C1_K * C1_K; ++w2) row[w2] = cacc[w2];
+      row[C1_K * C1_K] = csum;
+      if (pool_mode == 0) {
+#pragma unroll
+        for (int t = 0; t < S1_WSZ; ++t)
+          row[IB_CONV + t] = d2 * (float)(act_t)a1v[t];
+        row[IB_CONV + S1_WSZ] = d2;
+      }
+    } else if (wgrad_fuse) {
       // conv1 wgrad: this cell's 16 dz1 x its 8x8 input window (from LDS);
       // per-thread register accumulation, LDS-atomic combine per channel,
       // one global atomic per weight per block (in the final phase below).
@@ -368,7 +443,51 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
       unsafeAtomicAdd(loss_accum, sqrtf(ssum));
     }
   }
-  if (MODE == MODE_TRAIN && wgrad_fuse) {
+  if constexpr (INBLOCK) {
+    __syncthreads();
+    // Owners sum the 216 rows in a fixed order and store this image's slab
+    // row with plain stores; the kernel boundary publishes them.
+    const float* rows = inblock_rows();
+    float* out = grads + (size_t)b * GSLAB_LD;
+    if (tid < C1_CH * IB_CONV) {
+      // one owner per (channel, 5x5 weight | bias): the channel's 36 cells
+      const int o2 = tid / IB_CONV;
+      const int w2 = tid - o2 * IB_CONV;
+      const float* col = rows + o2 * S1_PIX * IB_LD + w2;
+      float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll
+      for (int c = 0; c < S1_PIX; c += 4) {
+        s0 += col[(c + 0) * IB_LD];
+        s1 += col[(c + 1) * IB_LD];
+        s2 += col[(c + 2) * IB_LD];
+        s3 += col[(c + 3) * IB_LD];
+      }
+      const float v = ((s0 + s1) + (s2 + s3)) * (1.0f / (float)C1_PIX);
+      out[w2 < C1_K * C1_K ? OFF_C1W + o2 * C1_K * C1_K + w2 : OFF_C1B + o2] =
+          v;
+    } else if (tid >= IB_POOL_T0 && tid < IB_POOL_T0 + 4 * (S1_WSZ + 1)) {
+      // four adjacent lanes per pool output, 54 rows each, 2-step shuffle
+      const int q = tid - IB_POOL_T0;
+      const int w2 = q >> 2;
+      const int part = q & 3;
+      float s = 0.f;
+      if (pool_mode == 0) {
+        const float* col =
+            rows + part * (S1_OUT / 4) * IB_LD + IB_CONV + w2;
+        float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+        for (int c = 0; c < S1_OUT / 4; c += 2) {
+          s0 += col[(c + 0) * IB_LD];
+          s1 += col[(c + 1) * IB_LD];
+        }
+        s = s0 + s1;
+      }
+      s += __shfl_xor(s, 1, 4);
+      s += __shfl_xor(s, 2, 4);
+      if (part == 0)
+        out[OFF_S1W + w2] = w2 < S1_WSZ ? s : s * (1.0f / (float)S1_OUT);
+    }
+  } else if (MODE == MODE_TRAIN && wgrad_fuse) {
     __syncthreads();
     // conv grads carry the reference 1/(24*24) factor; pool bias /216
     constexpr float inv_pix = 1.0f / (float)C1_PIX;
@@ -742,6 +861,91 @@ __global__ __launch_bounds__(256) void k_update(float* __restrict__ params,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Second kernel of the in-block weight-grad step: batch-reduce + SGD apply.
+// Every parameter has exactly one owner group of RU_LANES adjacent lanes, so
+// there are no atomics, no gradient bucket, no ticket and no fences:
+//   p <  173        g = sum_b gslab[b][p]           (scaled by the writer)
+//   fc weight (k,m) g = sum_b dz[b][k] * a2[b][m]
+//   fc bias k       g = sum_b dz[b][k]
+//   params[p] += step * g
+// Lane `sub` of a group takes images sub, sub+4, ...; RU_DEPTH of them are
+// loaded before the first is added, with clamped addresses and a select so
+// the loads stay unconditional.  Each lane adds in ascending image order
+// and the group combines with a fixed 2-step xor shuffle, so the result
+// does not depend on which block ran where or when.
+// ---------------------------------------------------------------------------
+constexpr int RU_LANES = 4;
+constexpr int RU_DEPTH = 8;
+constexpr int RU_PARAMS_PER_BLOCK = 256 / RU_LANES;  // 64
+constexpr int RU_BLOCKS =
+    (N_PARAMS + RU_PARAMS_PER_BLOCK - 1) / RU_PARAMS_PER_BLOCK;  // 37
+// Largest batch the step launcher gives to this pair of kernels (measured
+// crossover: pcnn_launch_step_inblock).
+constexpr int INBLOCK_MAX_B = 256;
+
+template <typename act_t>
+__global__ __launch_bounds__(256) void k_reduce_update(
+    const float* __restrict__ gslab, const act_t* __restrict__ a2g,
+    const float* __restrict__ dzg, float* __restrict__ params, float step,
+    int B) {
+  const int p = blockIdx.x * RU_PARAMS_PER_BLOCK + (threadIdx.x >> 2);
+  const int sub = threadIdx.x & (RU_LANES - 1);
+  // Lanes past the last parameter redo the last one and do not store: the
+  // whole group stays active for the shuffle.
+  const int pc = p < N_PARAMS ? p : N_PARAMS - 1;
+  constexpr int STEP_B = RU_LANES * RU_DEPTH;
+  float acc = 0.f;
+  if (pc < OFF_FW) {
+    for (int b0 = sub; b0 < B; b0 += STEP_B) {
+      float v[RU_DEPTH];
+#pragma unroll
+      for (int u = 0; u < RU_DEPTH; ++u) {
+        const int b = b0 + u * RU_LANES;
+        const int bc = b < B ? b : B - 1;
+        v[u] = gslab[(size_t)bc * GSLAB_LD + pc];
+        if (b >= B) v[u] = 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < RU_DEPTH; ++u) acc += v[u];
+    }
+  } else if (pc < OFF_FB) {
+    const int q = pc - OFF_FW;
+    const int k = q / FC_IN;
+    const int m = q - k * FC_IN;
+    for (int b0 = sub; b0 < B; b0 += STEP_B) {
+      float d[RU_DEPTH], a[RU_DEPTH];
+#pragma unroll
+      for (int u = 0; u < RU_DEPTH; ++u) {
+        const int b = b0 + u * RU_LANES;
+        const int bc = b < B ? b : B - 1;
+        d[u] = dzg[(size_t)bc * FC_OUT + k];
+        a[u] = ldf(a2g + (size_t)bc * FC_IN + m);
+        if (b >= B) d[u] = 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < RU_DEPTH; ++u) acc += d[u] * a[u];
+    }
+  } else {
+    const int k = pc - OFF_FB;
+    for (int b0 = sub; b0 < B; b0 += STEP_B) {
+      float d[RU_DEPTH];
+#pragma unroll
+      for (int u = 0; u < RU_DEPTH; ++u) {
+        const int b = b0 + u * RU_LANES;
+        const int bc = b < B ? b : B - 1;
+        d[u] = dzg[(size_t)bc * FC_OUT + k];
+        if (b >= B) d[u] = 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < RU_DEPTH; ++u) acc += d[u];
+    }
+  }
+  acc += __shfl_xor(acc, 1, RU_LANES);
+  acc += __shfl_xor(acc, 2, RU_LANES);
+  if (sub == 0 && p < N_PARAMS) params[p] += step * acc;
+}
+
 }  // namespace pcnn
 
 // ---------------------------------------------------------------------------
@@ -919,6 +1123,106 @@ int pcnn_launch_wgrad_update(const void* x, const void* a1, const void* a2,
   }
   return launch_wgrad_any(x, a1, a2, dz, dz2, dz1, grads, B, act_is_bf16,
                           chunk_imgs, roles, params, step, ticket, stream);
+}
+
+// First kernel of the in-block weight-grad step: k_fwdbwd<.., INBLOCK> in
+// train mode.  Writes a2, y, dz, the loss sum and rows [0, B) of gslab
+// ([>= B][GSLAB_LD] fp32); a1, dz1 and dz2 are not produced.
+int pcnn_launch_fwdbwd_inblock(const void* x, const float* params, void* a2,
+                               float* y, float* dz, const int* labels,
+                               float* loss_accum, float* gslab, int B,
+                               int act_is_bf16, int pool_mode, int loss_mode,
+                               void* stream) {
+  if (gslab == nullptr || dz == nullptr || B < 1)
+    return (int)hipErrorInvalidValue;
+  dim3 grid(B), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  if (act_is_bf16 == 1) {
+    hipLaunchKernelGGL((k_fwdbwd<bf16, MODE_TRAIN, true>), grid, block, 0, s,
+                       (const bf16*)x, params, (bf16*)nullptr, (bf16*)a2, y,
+                       dz, (float*)nullptr, (bf16*)nullptr, labels,
+                       loss_accum, (int*)nullptr, B, pool_mode, loss_mode,
+                       gslab, 0);
+  } else if (act_is_bf16 == 2) {
+    hipLaunchKernelGGL((k_fwdbwd<fp16, MODE_TRAIN, true>), grid, block, 0, s,
+                       (const fp16*)x, params, (fp16*)nullptr, (fp16*)a2, y,
+                       dz, (float*)nullptr, (fp16*)nullptr, labels,
+                       loss_accum, (int*)nullptr, B, pool_mode, loss_mode,
+                       gslab, 0);
+  } else {
+    hipLaunchKernelGGL((k_fwdbwd<float, MODE_TRAIN, true>), grid, block, 0, s,
+                       (const float*)x, params, (float*)nullptr, (float*)a2,
+                       y, dz, (float*)nullptr, (float*)nullptr, labels,
+                       loss_accum, (int*)nullptr, B, pool_mode, loss_mode,
+                       gslab, 0);
+  }
+  return (int)hipGetLastError();
+}
+
+// Second kernel of the in-block weight-grad step (k_reduce_update).
+int pcnn_launch_reduce_update(const float* gslab, const void* a2,
+                              const float* dz, float* params, float step,
+                              int B, int act_is_bf16, void* stream) {
+  if (gslab == nullptr || params == nullptr || B < 1)
+    return (int)hipErrorInvalidValue;
+  dim3 grid(RU_BLOCKS), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  if (act_is_bf16 == 1) {
+    hipLaunchKernelGGL((k_reduce_update<bf16>), grid, block, 0, s, gslab,
+                       (const bf16*)a2, dz, params, step, B);
+  } else if (act_is_bf16 == 2) {
+    hipLaunchKernelGGL((k_reduce_update<fp16>), grid, block, 0, s, gslab,
+                       (const fp16*)a2, dz, params, step, B);
+  } else {
+    hipLaunchKernelGGL((k_reduce_update<float>), grid, block, 0, s, gslab,
+                       (const float*)a2, dz, params, step, B);
+  }
+  return (int)hipGetLastError();
+}
+
+// Largest batch that runs the in-block weight-grad step; above it the step
+// launcher below runs k_fwdbwd + k_wgrad_update as before.
+int pcnn_inblock_max_batch() { return INBLOCK_MAX_B; }
+
+// One whole single-GPU training step with in-block weight grads:
+// k_fwdbwd<INBLOCK> -> k_reduce_update.  `grads` and `ticket` are only
+// touched by the large-batch fallback and read all-zero / 0 afterwards
+// either way.
+int pcnn_launch_step_inblock(const void* x, float* params, void* a1, void* a2,
+                             float* y, float* dz, float* dz2, void* dz1,
+                             const int* labels, float* loss_accum,
+                             float* grads, int* ticket, float* gslab,
+                             float step, int B, int act_is_bf16,
+                             int pool_mode, int loss_mode, int chunk_imgs,
+                             void* stream) {
+  // k_reduce_update walks the batch with 4 lanes per parameter, so its cost
+  // grows linearly with B while k_wgrad_update spreads a larger batch over
+  // more blocks.  Measured (MI355X, bf16, us/step, in-block vs
+  // k_wgrad_update in one job, in-block at every size): B=16 12.33 vs
+  // 17.08, 64 13.60 vs 18.60, 256 21.22 vs 23.64, 1024 54.08 vs 42.16,
+  // 4096 175.9 vs 100.7 (profiles/r4).  256 is the last measured gain,
+  // 1024 the first measured loss; nothing was measured in between, so the
+  // true crossover lies somewhere in (256, 1024) and batches there keep the
+  // k_wgrad_update step without having been compared.
+  if (B > INBLOCK_MAX_B) {
+    // Role mask as Trainer._wroles builds it: all roles, minus the pool
+    // role under max pooling.  The fc-only mask (4) belongs to fuse_wgrad,
+    // which excludes this step.
+    int err = pcnn_launch_fwdbwd_ex2(x, params, a1, a2, y, dz, dz2, dz1,
+                                     labels, loss_accum, nullptr, B,
+                                     act_is_bf16, MODE_TRAIN, pool_mode,
+                                     loss_mode, grads, 0, stream);
+    if (err != 0) return err;
+    return pcnn_launch_wgrad_update(x, a1, a2, dz, dz2, dz1, grads, params,
+                                    step, ticket, B, act_is_bf16, chunk_imgs,
+                                    pool_mode == 1 ? 5 : 7, stream);
+  }
+  int err = pcnn_launch_fwdbwd_inblock(x, params, a2, y, dz, labels,
+                                       loss_accum, gslab, B, act_is_bf16,
+                                       pool_mode, loss_mode, stream);
+  if (err != 0) return err;
+  return pcnn_launch_reduce_update(gslab, a2, dz, params, step, B,
+                                   act_is_bf16, stream);
 }
 
 int pcnn_launch_wgrad(const void* x, const void* a1, const void* a2,

@@ -45,6 +45,15 @@ constexpr int OFF_FW = OFF_S1B + 1;                    // 173
 constexpr int OFF_FB = OFF_FW + FC_WSZ;                // 2333
 constexpr int N_PARAMS = OFF_FB + FC_OUT;              // 2343
 
+// In-block weight-grad step: per-image slab of conv/pool gradient sums,
+// gslab[max_batch][GSLAB_LD] fp32.  Columns [0, OFF_FW) are laid out like
+// the flat parameter vector (conv w, conv b, pool w, pool b); columns 173-175
+// are padding and never read.  The reference scale factors are applied by
+// the kernel that WRITES the slab (k_fwdbwd<.., INBLOCK>): 1/576 on the conv
+// weight and bias sums, 1/216 on the pool bias, so k_reduce_update adds
+// slab rows as they are.  Under max pooling the pool columns hold zeros.
+constexpr int GSLAB_LD = 176;
+
 // Reference hyperparameters (Sequential/layer.h:12-13).
 constexpr float REF_DT = 1.0e-1f;
 constexpr float REF_THRESHOLD = 1.0e-2f;

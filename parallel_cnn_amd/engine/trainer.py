@@ -3,8 +3,11 @@ Main.cpp `learn()` / `test()` / `classify()`.
 
 Backends:
   * "hip"      — the gfx950 HIP kernels (2 launches per step on one GPU:
-                 fwd+bwd-data, then weight-grad with the SGD update as
-                 its tail; 3 wherever something sits between weight-grad
+                 fwd+bwd-data with the conv/pool weight grads formed in
+                 the per-image block, then slab reduce + fc weight grads
+                 + SGD update; or, with PCNN_LENET_WGRAD=grid, fwd+bwd-data
+                 then the grid weight-grad kernel with the update as its
+                 tail; 3 wherever something sits between weight-grad
                  and update — all-reduce, accumulation, phase timers);
   * "cpu"      — the native C++ reference ops (threaded, race-free);
   * "torchref" — the pure-PyTorch fp32 oracle (tests/debugging).
@@ -53,6 +56,10 @@ class Workspace:
         # arrival ticket of the update-fused weight-grad kernel: reads 0
         # between launches (the last block to arrive resets it)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        # per-image conv/pool gradient sums of the in-block weight-grad
+        # step (layout and scaling: GSLAB_LD in csrc/lenet_dims.h)
+        self.gslab = torch.zeros(B, S.GSLAB_LD, dtype=torch.float32,
+                                 device=dev)
 
 
 class Trainer:
@@ -101,6 +108,15 @@ class Trainer:
             raise ValueError(
                 f"PCNN_LENET_STEP must be 3 or 2, got {mode!r}")
         self._step_mode = int(mode)
+        # how the two-launch step forms the weight gradients, read once
+        # here: PCNN_LENET_WGRAD=inblock (default) computes the conv/pool
+        # grads inside k_fwdbwd and finishes with k_reduce_update; grid runs
+        # k_wgrad_update.  No effect under PCNN_LENET_STEP=3.
+        wg = os.environ.get("PCNN_LENET_WGRAD", "inblock")
+        if wg not in ("inblock", "grid"):
+            raise ValueError(
+                f"PCNN_LENET_WGRAD must be inblock or grid, got {wg!r}")
+        self._wgrad_inblock = wg == "inblock"
 
     def _fused_step_mode(self) -> int:
         """2 when the update may run inside the wgrad launch: nothing may
@@ -111,6 +127,21 @@ class Trainer:
                 and self.timers is None and not pdist.is_distributed()):
             return 2
         return 3
+
+    def _use_inblock(self) -> bool:
+        """The in-block weight-grad step applies wherever the two-launch
+        step does."""
+        return self._wgrad_inblock and self._fused_step_mode() == 2
+
+    def _step_inblock(self, x: torch.Tensor, labels: torch.Tensor, B: int,
+                      stream: int) -> None:
+        m, w = self.model, self.ws
+        self._C.hip_step_inblock(x, m.params, w.a1, w.a2, w.y, w.dz, w.dz2,
+                                 w.dz1, labels, w.loss_accum, m.grads,
+                                 w.ticket, w.gslab,
+                                 self.cfg.dt * self._update_scale(B), B,
+                                 self.cfg.wgrad_chunk, stream,
+                                 self._pool_mode, self._loss_mode)
 
     # ------------------------------------------------------------------ util
     def _update_scale(self, local_batch: int) -> float:
@@ -154,7 +185,9 @@ class Trainer:
             self._accum = 0
         m, w = self.model, self.ws
         scale = self._update_scale(B)
-        if self.backend == "hip":
+        if self.backend == "hip" and self._use_inblock():
+            self._step_inblock(x, labels, B, self._sh)
+        elif self.backend == "hip":
             stream = self._sh
             self._C.hip_fwdbwd(x, m.params, w.a1, w.a2, w.y, w.dz, w.dz2,
                                w.dz1, labels, w.loss_accum, w.correct_accum,
@@ -304,6 +337,9 @@ class Trainer:
     def _graph_body(self, B: int) -> None:
         m, w = self.model, self.ws
         stream = native.current_stream_handle()
+        if self._use_inblock():
+            self._step_inblock(self._gx, self._gl, B, stream)
+            return
         self._C.hip_fwdbwd(self._gx, m.params, w.a1, w.a2, w.y, w.dz, w.dz2,
                            w.dz1, self._gl, w.loss_accum, w.correct_accum,
                            B, MODE_TRAIN, stream, self._pool_mode,
@@ -351,8 +387,9 @@ class Trainer:
                 w.a1, w.a2, w.y, w.dz, w.dz2, w.dz1, w.loss_accum, B, steps,
                 self.cfg.wgrad_chunk, self.cfg.dt * self._update_scale(B),
                 native.current_stream_handle(), self._pool_mode,
-                self._loss_mode, self._fuse, self._fused_step_mode(),
-                w.ticket)
+                self._loss_mode, self._fuse,
+                4 if self._use_inblock() else self._fused_step_mode(),
+                w.ticket, w.gslab)
             self._samples_seen += B * steps
             self.global_step += steps
         else:

@@ -35,5 +35,7 @@ OFF_FW = OFF_S1B + 1            # 173
 OFF_FB = OFF_FW + FC_WSZ        # 2333
 N_PARAMS = OFF_FB + FC_OUT      # 2343
 
+GSLAB_LD = 176                  # per-image gradient slab row (lenet_dims.h)
+
 REF_DT = 0.1                    # Sequential/layer.h:12
 REF_THRESHOLD = 1.0e-2          # Sequential/layer.h:13
