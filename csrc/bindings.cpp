@@ -18,6 +18,9 @@ double cpu_backward(at::Tensor x, at::Tensor params, at::Tensor a1,
                     at::Tensor dz, at::Tensor dz2, at::Tensor dz1,
                     at::Tensor grads, int64_t pool_mode, int64_t loss_mode);
 void cpu_update(at::Tensor params, at::Tensor grads, double dt, double scale);
+void cpu_update_momentum(at::Tensor params, at::Tensor grads, at::Tensor vel,
+                         double dt, double scale, double mu, double wd,
+                         bool nesterov);
 }  // namespace pcnn
 
 extern "C" {
@@ -66,6 +69,44 @@ int pcnn_launch_step_inblock(const void* x, float* params, void* a1, void* a2,
                              float step, int B, int act_is_bf16,
                              int pool_mode, int loss_mode, int chunk_imgs,
                              void* stream);
+// momentum variants: scale and dt apart, vel = fp32 velocity bucket
+int pcnn_launch_update_mom(float* params, float* grads, float* vel,
+                           float scale, float dt, float mu, float wd,
+                           int nesterov, void* stream);
+int pcnn_launch_wgrad_update_mom(const void* x, const void* a1,
+                                 const void* a2, const float* dz,
+                                 const float* dz2, const void* dz1,
+                                 float* grads, float* params, float* vel,
+                                 float scale, float dt, float mu, float wd,
+                                 int nesterov, int* ticket, int B,
+                                 int act_is_bf16, int chunk_imgs, int roles,
+                                 void* stream);
+int pcnn_launch_reduce_update_mom(const float* gslab, const void* a2,
+                                  const float* dz, float* params, float* vel,
+                                  float scale, float dt, float mu, float wd,
+                                  int nesterov, int B, int act_is_bf16,
+                                  void* stream);
+int pcnn_launch_step_inblock_mom(const void* x, float* params, float* vel,
+                                 void* a1, void* a2, float* y, float* dz,
+                                 float* dz2, void* dz1, const int* labels,
+                                 float* loss_accum, float* grads, int* ticket,
+                                 float* gslab, float scale, float dt,
+                                 float mu, float wd, int nesterov, int B,
+                                 int act_is_bf16, int pool_mode,
+                                 int loss_mode, int chunk_imgs,
+                                 void* stream);
+int pcnn_deep_update_cast_mom(float* params, float* grads, float* vel,
+                              long long n, float scale, float dt, float mu,
+                              float wd, int nesterov, void* wbuf,
+                              int n_stages, const int* R, const int* C,
+                              const int* K, const int* Cin,
+                              const long long* w_off, const long long* bf_off,
+                              const long long* bfT_off,
+                              const long long* rot_off,
+                              const long long* p8_off, void* stream);
+int pcnn_deep_update_mom(float* params, float* grads, float* vel, long long n,
+                         float scale, float dt, float mu, float wd,
+                         int nesterov, void* stream);
 const char* pcnn_hip_error_string(int err);
 // deep (general conv) kernels — csrc/hip/conv_kernels.hip
 int pcnn_deep_im2col(const void* x, void* cols, int B, int H, int W, int Cin,
@@ -254,6 +295,57 @@ void hip_wgrad_update(at::Tensor x, at::Tensor a1, at::Tensor a2,
             "wgrad_update");
 }
 
+// Velocity bucket of the momentum update variants.
+float* vel_ptr(const at::Tensor& vel, const at::Tensor& params) {
+  TORCH_CHECK(vel.is_cuda() && vel.scalar_type() == at::kFloat &&
+                  vel.is_contiguous() && vel.numel() == params.numel(),
+              "vel must be a contiguous device fp32 tensor with the same "
+              "numel as params");
+  return vel.data_ptr<float>();
+}
+
+// hip_update with momentum / Nesterov / weight decay (k_update_mom).
+void hip_update_momentum(at::Tensor params, at::Tensor grads, at::Tensor vel,
+                         double dt, double scale, double mu, double wd,
+                         bool nesterov, int64_t stream) {
+  TORCH_CHECK(params.is_cuda() && grads.is_cuda() &&
+                  params.numel() == pcnn::N_PARAMS &&
+                  grads.numel() == pcnn::N_PARAMS,
+              "params/grads must be the flat device buckets");
+  check_hip(pcnn_launch_update_mom(params.data_ptr<float>(),
+                                   grads.data_ptr<float>(),
+                                   vel_ptr(vel, params), (float)scale,
+                                   (float)dt, (float)mu, (float)wd,
+                                   nesterov ? 1 : 0, (void*)stream),
+            "update_momentum");
+}
+
+// hip_wgrad_update with the momentum tail (k_wgrad_update_mom).
+void hip_wgrad_update_momentum(at::Tensor x, at::Tensor a1, at::Tensor a2,
+                               at::Tensor dz, at::Tensor dz2, at::Tensor dz1,
+                               at::Tensor grads, at::Tensor params,
+                               at::Tensor vel, double dt, double scale,
+                               double mu, double wd, bool nesterov,
+                               at::Tensor ticket, int64_t B,
+                               int64_t chunk_imgs, int64_t roles,
+                               int64_t stream) {
+  int f = act_flag(x);
+  TORCH_CHECK(dz1.scalar_type() == x.scalar_type(),
+              "dz1 must match the activation dtype");
+  TORCH_CHECK(params.is_cuda() && grads.is_cuda() &&
+                  params.numel() == pcnn::N_PARAMS &&
+                  grads.numel() == pcnn::N_PARAMS,
+              "params/grads must be the flat device buckets");
+  check_hip(pcnn_launch_wgrad_update_mom(
+                x.data_ptr(), a1.data_ptr(), a2.data_ptr(),
+                dz.data_ptr<float>(), dz2.data_ptr<float>(), dz1.data_ptr(),
+                grads.data_ptr<float>(), params.data_ptr<float>(),
+                vel_ptr(vel, params), (float)scale, (float)dt, (float)mu,
+                (float)wd, nesterov ? 1 : 0, ticket_ptr(ticket), (int)B, f,
+                (int)chunk_imgs, (int)roles, (void*)stream),
+            "wgrad_update_momentum");
+}
+
 float* gslab_ptr(const at::Tensor& gslab, int64_t B) {
   TORCH_CHECK(gslab.is_cuda() && gslab.scalar_type() == at::kFloat &&
                   gslab.is_contiguous() &&
@@ -328,6 +420,72 @@ void hip_step_inblock(at::Tensor x, at::Tensor params, at::Tensor a1,
             "step_inblock");
 }
 
+// Second kernel of the in-block step on its own, momentum form
+// (k_reduce_update_mom): slab rows [0, B), a2 and dz in, params and vel
+// updated.
+void hip_reduce_update_momentum(at::Tensor gslab, at::Tensor a2,
+                                at::Tensor dz, at::Tensor params,
+                                at::Tensor vel, double dt, double scale,
+                                double mu, double wd, bool nesterov,
+                                int64_t B, int64_t stream) {
+  TORCH_CHECK(params.is_cuda() && params.numel() == pcnn::N_PARAMS,
+              "params must be the flat device bucket");
+  TORCH_CHECK(B >= 1 && a2.is_cuda() && a2.numel() >= B * pcnn::S1_OUT &&
+                  dz.is_cuda() && dz.scalar_type() == at::kFloat &&
+                  dz.numel() >= B * pcnn::FC_OUT,
+              "buffers too small for B");
+  check_hip(pcnn_launch_reduce_update_mom(
+                gslab_ptr(gslab, B), a2.data_ptr(), dz.data_ptr<float>(),
+                params.data_ptr<float>(), vel_ptr(vel, params), (float)scale,
+                (float)dt, (float)mu, (float)wd, nesterov ? 1 : 0, (int)B,
+                act_flag(a2), (void*)stream),
+            "reduce_update_momentum");
+}
+
+// hip_step_inblock with the momentum update (k_fwdbwd<INBLOCK> ->
+// k_reduce_update_mom; above _C.INBLOCK_MAX_BATCH k_fwdbwd ->
+// k_wgrad_update_mom).
+void hip_step_inblock_momentum(at::Tensor x, at::Tensor params,
+                               at::Tensor vel, at::Tensor a1, at::Tensor a2,
+                               at::Tensor y, at::Tensor dz, at::Tensor dz2,
+                               at::Tensor dz1, at::Tensor labels,
+                               at::Tensor loss_accum, at::Tensor grads,
+                               at::Tensor ticket, at::Tensor gslab, double dt,
+                               double scale, double mu, double wd,
+                               bool nesterov, int64_t B, int64_t chunk_imgs,
+                               int64_t stream, int64_t pool_mode,
+                               int64_t loss_mode) {
+  TORCH_CHECK(x.is_cuda() && params.is_cuda(), "expected device tensors");
+  TORCH_CHECK(labels.scalar_type() == at::kInt, "labels must be int32");
+  TORCH_CHECK(dz1.scalar_type() == x.scalar_type() &&
+                  a2.scalar_type() == x.scalar_type(),
+              "a2/dz1 must match the activation dtype");
+  TORCH_CHECK(params.numel() == pcnn::N_PARAMS &&
+                  grads.numel() == pcnn::N_PARAMS,
+              "params/grads must be the flat device buckets");
+  TORCH_CHECK(B >= 1 && x.numel() >= B * pcnn::IN_PIX &&
+                  a2.numel() >= B * pcnn::S1_OUT &&
+                  y.numel() >= B * pcnn::FC_OUT &&
+                  dz.numel() >= B * pcnn::FC_OUT && labels.numel() >= B,
+              "buffers too small for B");
+  TORCH_CHECK(B <= pcnn_inblock_max_batch() ||
+                  (a1.numel() >= B * pcnn::C1_OUT &&
+                   dz1.numel() >= B * pcnn::C1_OUT &&
+                   dz2.numel() >= B * pcnn::S1_OUT),
+              "a1/dz1/dz2 too small for the large-batch path");
+  check_hip(pcnn_launch_step_inblock_mom(
+                x.data_ptr(), params.data_ptr<float>(), vel_ptr(vel, params),
+                a1.data_ptr(), a2.data_ptr(), y.data_ptr<float>(),
+                dz.data_ptr<float>(), dz2.data_ptr<float>(), dz1.data_ptr(),
+                labels.data_ptr<int>(), loss_accum.data_ptr<float>(),
+                grads.data_ptr<float>(), ticket_ptr(ticket),
+                gslab_ptr(gslab, B), (float)scale, (float)dt, (float)mu,
+                (float)wd, nesterov ? 1 : 0, (int)B, act_flag(x),
+                (int)pool_mode, (int)loss_mode, (int)chunk_imgs,
+                (void*)stream),
+            "step_inblock_momentum");
+}
+
 // Single-GPU fused training loop: enqueues `steps` full training steps
 // from C++, cycling a device-resident batch pool.  step_mode 3 is
 // fwd+bwd-data -> wgrad -> update; step_mode 2 is fwd+bwd-data ->
@@ -344,7 +502,14 @@ void hip_train_steps(at::Tensor x_pool, at::Tensor labels_pool,
                      double step_scale, int64_t stream, int64_t pool_mode,
                      int64_t loss_mode, int64_t wgrad_fuse,
                      int64_t step_mode, at::Tensor ticket,
-                     at::Tensor gslab) {
+                     at::Tensor gslab, at::Tensor vel, double dt,
+                     double scale, double mu, double wd, bool nesterov) {
+  // a non-empty vel selects the momentum update in every step mode; dt and
+  // scale then replace the pre-multiplied step_scale
+  float* vp = vel.numel() ? vel_ptr(vel, params) : nullptr;
+  const float o_scale = (float)scale, o_dt = (float)dt, o_mu = (float)mu,
+              o_wd = (float)wd;
+  const int o_nes = nesterov ? 1 : 0;
   TORCH_CHECK(step_mode == 3 || step_mode == 2 || step_mode == 4,
               "step_mode must be 3, 2 or 4");
   TORCH_CHECK(step_mode == 3 || !wgrad_fuse,
@@ -371,6 +536,17 @@ void hip_train_steps(at::Tensor x_pool, at::Tensor labels_pool,
     const int64_t i = st % P;
     const void* xb = xp + (size_t)i * B * pcnn::IN_PIX * esz;
     const int* lb = lp + i * B;
+    if (slab != nullptr && vp != nullptr) {
+      check_hip(pcnn_launch_step_inblock_mom(
+                    xb, pp, vp, a1.data_ptr(), a2.data_ptr(),
+                    y.data_ptr<float>(), dz.data_ptr<float>(),
+                    dz2.data_ptr<float>(), dz1.data_ptr(), lb,
+                    loss_accum.data_ptr<float>(), gp, tk, slab, o_scale,
+                    o_dt, o_mu, o_wd, o_nes, (int)B, f, (int)pool_mode,
+                    (int)loss_mode, (int)chunk_imgs, s),
+                "train_steps/step_inblock_momentum");
+      continue;
+    }
     if (slab != nullptr) {
       check_hip(pcnn_launch_step_inblock(
                     xb, pp, a1.data_ptr(), a2.data_ptr(), y.data_ptr<float>(),
@@ -390,6 +566,15 @@ void hip_train_steps(at::Tensor x_pool, at::Tensor labels_pool,
                                      (int)B, f, 0, (int)pool_mode,
                                      (int)loss_mode, gp, (int)wgrad_fuse, s),
               "train_steps/fwdbwd");
+    if (tk != nullptr && vp != nullptr) {
+      check_hip(pcnn_launch_wgrad_update_mom(
+                    xb, a1.data_ptr(), a2.data_ptr(), dz.data_ptr<float>(),
+                    dz2.data_ptr<float>(), dz1.data_ptr(), gp, pp, vp,
+                    o_scale, o_dt, o_mu, o_wd, o_nes, tk, (int)B, f,
+                    (int)chunk_imgs, wroles, s),
+                "train_steps/wgrad_update_momentum");
+      continue;
+    }
     if (tk != nullptr) {
       check_hip(pcnn_launch_wgrad_update(
                     xb, a1.data_ptr(), a2.data_ptr(), dz.data_ptr<float>(),
@@ -404,6 +589,12 @@ void hip_train_steps(at::Tensor x_pool, at::Tensor labels_pool,
                                    dz1.data_ptr(), gp, (int)B, f,
                                    (int)chunk_imgs, wroles, s),
               "train_steps/wgrad");
+    if (vp != nullptr) {
+      check_hip(pcnn_launch_update_mom(pp, gp, vp, o_scale, o_dt, o_mu, o_wd,
+                                       o_nes, s),
+                "train_steps/update_momentum");
+      continue;
+    }
     check_hip(pcnn_launch_update(pp, gp, (float)step_scale, s),
               "train_steps/update");
   }
@@ -513,6 +704,49 @@ void deep_update_cast(at::Tensor params, at::Tensor grads, double step,
                                   Ci, Ki, Cini, wo, bo, bto, ro, po,
                                   (void*)stream),
             "deep_update_cast");
+}
+
+// deep_update_cast with momentum / Nesterov / weight decay: the bf16 images
+// are cast from the post-momentum value.
+void deep_update_cast_momentum(at::Tensor params, at::Tensor grads,
+                               at::Tensor vel, double dt, double scale,
+                               double mu, double wd, bool nesterov,
+                               at::Tensor wbuf, std::vector<int64_t> R,
+                               std::vector<int64_t> C, std::vector<int64_t> K,
+                               std::vector<int64_t> Cin,
+                               std::vector<int64_t> w_off,
+                               std::vector<int64_t> bf_off,
+                               std::vector<int64_t> bfT_off,
+                               std::vector<int64_t> rot_off,
+                               std::vector<int64_t> p8_off, int64_t stream) {
+  const size_t n = R.size();
+  TORCH_CHECK(n >= 1 && n <= 8, "deep_update_cast_momentum: 1..8 stages");
+  TORCH_CHECK(C.size() == n && K.size() == n && Cin.size() == n &&
+                  w_off.size() == n && bf_off.size() == n &&
+                  bfT_off.size() == n && rot_off.size() == n &&
+                  (p8_off.empty() || p8_off.size() == n),
+              "deep_update_cast_momentum: descriptor length mismatch");
+  TORCH_CHECK(grads.numel() == params.numel(), "grads/params size mismatch");
+  int Ri[8], Ci[8], Ki[8], Cini[8];
+  long long wo[8], bo[8], bto[8], ro[8], po[8];
+  for (size_t s = 0; s < n; ++s) {
+    Ri[s] = (int)R[s];
+    Ci[s] = (int)C[s];
+    Ki[s] = (int)K[s];
+    Cini[s] = (int)Cin[s];
+    wo[s] = w_off[s];
+    bo[s] = bf_off[s];
+    bto[s] = bfT_off[s];
+    ro[s] = rot_off[s];
+    po[s] = p8_off.empty() ? -1 : p8_off[s];
+  }
+  check_hip(pcnn_deep_update_cast_mom(
+                params.data_ptr<float>(), grads.data_ptr<float>(),
+                vel_ptr(vel, params), params.numel(), (float)scale, (float)dt,
+                (float)mu, (float)wd, nesterov ? 1 : 0, wbuf.data_ptr(),
+                (int)n, Ri, Ci, Ki, Cini, wo, bo, bto, ro, po,
+                (void*)stream),
+            "deep_update_cast_momentum");
 }
 
 void deep_wgrad_multi(std::vector<at::Tensor> a,
@@ -696,6 +930,18 @@ void deep_update(at::Tensor params, at::Tensor grads, double step,
             "deep_update");
 }
 
+void deep_update_momentum(at::Tensor params, at::Tensor grads,
+                          at::Tensor vel, double dt, double scale, double mu,
+                          double wd, bool nesterov, int64_t stream) {
+  TORCH_CHECK(grads.numel() == params.numel(), "grads/params size mismatch");
+  check_hip(pcnn_deep_update_mom(params.data_ptr<float>(),
+                                 grads.data_ptr<float>(),
+                                 vel_ptr(vel, params), params.numel(),
+                                 (float)scale, (float)dt, (float)mu,
+                                 (float)wd, nesterov ? 1 : 0, (void*)stream),
+            "deep_update_momentum");
+}
+
 void deep_mfma_selftest(at::Tensor A, at::Tensor Bm, at::Tensor D,
                         int64_t stream) {
   check_hip(pcnn_deep_mfma_selftest(A.data_ptr<float>(),
@@ -717,6 +963,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dz"), py::arg("dz2"), py::arg("dz1"), py::arg("grads"),
         py::arg("pool_mode") = 0, py::arg("loss_mode") = 0);
   m.def("cpu_update", &pcnn::cpu_update);
+  m.def("cpu_update_momentum", &pcnn::cpu_update_momentum, py::arg("params"),
+        py::arg("grads"), py::arg("vel"), py::arg("dt"), py::arg("scale"),
+        py::arg("mu"), py::arg("wd"), py::arg("nesterov"));
   m.def("hip_fwdbwd", &hip_fwdbwd, py::arg("x"), py::arg("params"),
         py::arg("a1"), py::arg("a2"), py::arg("y"), py::arg("dz"),
         py::arg("dz2"), py::arg("dz1"), py::arg("labels"),
@@ -735,7 +984,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("stream"), py::arg("pool_mode") = 0,
         py::arg("loss_mode") = 0, py::arg("wgrad_fuse") = 0,
         py::arg("step_mode") = 3, py::arg("ticket") = at::empty({0}),
-        py::arg("gslab") = at::empty({0}));
+        py::arg("gslab") = at::empty({0}), py::arg("vel") = at::empty({0}),
+        py::arg("dt") = 0.0, py::arg("scale") = 1.0, py::arg("mu") = 0.0,
+        py::arg("wd") = 0.0, py::arg("nesterov") = false);
+  m.def("hip_update_momentum", &hip_update_momentum, py::arg("params"),
+        py::arg("grads"), py::arg("vel"), py::arg("dt"), py::arg("scale"),
+        py::arg("mu"), py::arg("wd"), py::arg("nesterov"),
+        py::arg("stream"));
+  m.def("hip_wgrad_update_momentum", &hip_wgrad_update_momentum,
+        py::arg("x"), py::arg("a1"), py::arg("a2"), py::arg("dz"),
+        py::arg("dz2"), py::arg("dz1"), py::arg("grads"), py::arg("params"),
+        py::arg("vel"), py::arg("dt"), py::arg("scale"), py::arg("mu"),
+        py::arg("wd"), py::arg("nesterov"), py::arg("ticket"), py::arg("B"),
+        py::arg("chunk_imgs"), py::arg("roles"), py::arg("stream"));
+  m.def("hip_reduce_update_momentum", &hip_reduce_update_momentum,
+        py::arg("gslab"), py::arg("a2"), py::arg("dz"), py::arg("params"),
+        py::arg("vel"), py::arg("dt"), py::arg("scale"), py::arg("mu"),
+        py::arg("wd"), py::arg("nesterov"), py::arg("B"), py::arg("stream"));
+  m.def("hip_step_inblock_momentum", &hip_step_inblock_momentum,
+        py::arg("x"), py::arg("params"), py::arg("vel"), py::arg("a1"),
+        py::arg("a2"), py::arg("y"), py::arg("dz"), py::arg("dz2"),
+        py::arg("dz1"), py::arg("labels"), py::arg("loss_accum"),
+        py::arg("grads"), py::arg("ticket"), py::arg("gslab"), py::arg("dt"),
+        py::arg("scale"), py::arg("mu"), py::arg("wd"), py::arg("nesterov"),
+        py::arg("B"), py::arg("chunk_imgs"), py::arg("stream"),
+        py::arg("pool_mode") = 0, py::arg("loss_mode") = 0);
   m.def("hip_fwdbwd_inblock", &hip_fwdbwd_inblock, py::arg("x"),
         py::arg("params"), py::arg("a2"), py::arg("y"), py::arg("dz"),
         py::arg("labels"), py::arg("loss_accum"), py::arg("gslab"),
@@ -791,6 +1064,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("deep_fc_bwd", &deep_fc_bwd);
   m.def("deep_fc_wgrad", &deep_fc_wgrad);
   m.def("deep_update", &deep_update);
+  m.def("deep_update_momentum", &deep_update_momentum);
+  m.def("deep_update_cast_momentum", &deep_update_cast_momentum);
   m.def("deep_mfma_selftest", &deep_mfma_selftest);
   m.attr("N_PARAMS") = pcnn::N_PARAMS;
   m.attr("GSLAB_LD") = pcnn::GSLAB_LD;

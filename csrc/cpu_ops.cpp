@@ -313,4 +313,28 @@ void cpu_update(at::Tensor params, at::Tensor grads, double dt, double scale) {
   }
 }
 
+// Momentum / Nesterov / weight decay, ascent convention (any flat size):
+//   u = scale*g - wd*p;  v = mu*v + u;  p += dt*v  (nesterov: dt*(u + mu*v))
+//   g = 0.
+void cpu_update_momentum(at::Tensor params, at::Tensor grads, at::Tensor vel,
+                         double dt, double scale, double mu, double wd,
+                         bool nesterov) {
+  const int64_t n = params.numel();
+  check_cpu_f32(params, "params", n);
+  check_cpu_f32(grads, "grads", n);
+  check_cpu_f32(vel, "vel", n);
+  float* pp = params.data_ptr<float>();
+  float* gp = grads.data_ptr<float>();
+  float* vp = vel.data_ptr<float>();
+  const float fdt = (float)dt, fs = (float)scale, fmu = (float)mu,
+              fwd = (float)wd;
+  for (int64_t i = 0; i < n; ++i) {
+    const float u = fs * gp[i] - fwd * pp[i];
+    const float v = fmu * vp[i] + u;
+    vp[i] = v;
+    pp[i] += fdt * (nesterov ? u + fmu * v : v);
+    gp[i] = 0.f;
+  }
+}
+
 }  // namespace pcnn

@@ -1933,6 +1933,73 @@ __global__ void k_update_n(float* __restrict__ params,
   }
 }
 
+// Momentum / Nesterov / weight-decay update (ascent convention):
+//   u = scale*g - wd*p;  v = mu*v + u;  p += dt*v   (nesterov: dt*(u+mu*v))
+// vel is the fp32 velocity bucket in the params layout.  A conv-weight pad
+// row has p = g = v = 0 and stays there under these formulas.
+struct MomArgs {
+  float scale, dt, mu, wd;
+  int nesterov;
+};
+
+__device__ __forceinline__ float mom_apply(float p, float g, float& v,
+                                           const MomArgs& o) {
+  const float u = o.scale * g - o.wd * p;
+  v = o.mu * v + u;
+  return p + o.dt * (o.nesterov ? u + o.mu * v : v);
+}
+
+// k_update_cast_all with the momentum update: the bf16 images are cast
+// from the post-momentum value.
+__global__ void k_update_cast_all_mom(float* __restrict__ params,
+                                      float* __restrict__ grads,
+                                      float* __restrict__ vel, long long n,
+                                      MomArgs o, __bf16* __restrict__ wbuf,
+                                      CastDescs d) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float v = vel[i];
+  const float pnew = mom_apply(params[i], grads[i], v, o);
+  params[i] = pnew;
+  vel[i] = v;
+  grads[i] = 0.f;
+  for (int s = 0; s < d.n; ++s) {
+    const long long q = i - d.w_off[s];
+    if (q < 0 || q >= d.cum[s + 1] - d.cum[s]) continue;
+    const int C = d.C[s];
+    const int kc = (int)(q / C);
+    const int c = (int)(q - (long long)kc * C);
+    const __bf16 bv = (__bf16)pnew;
+    wbuf[d.bf_off[s] + q] = bv;
+    wbuf[d.bfT_off[s] + (long long)c * d.R[s] + kc] = bv;
+    const int Cin = d.Cin[s], K = d.K[s];
+    if (kc < K * K * Cin) {
+      const int ci = kc % Cin;
+      const int p2 = kc / Cin;
+      const int ki = p2 / K, kj = p2 - ki * K;
+      const int col = ((K - 1 - ki) * K + (K - 1 - kj)) * C + c;
+      wbuf[d.rot_off[s] + (long long)ci * (K * K * C) + col] = bv;
+      if (d.p8_off[s] >= 0)
+        wbuf[d.p8_off[s] + (long long)c * (K * K * 8) + p2 * 8 + ci] = bv;
+    }
+    break;
+  }
+}
+
+// k_update_n with the momentum update.
+__global__ void k_update_n_mom(float* __restrict__ params,
+                               float* __restrict__ grads,
+                               float* __restrict__ vel, long long n,
+                               MomArgs o) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    float v = vel[i];
+    params[i] = mom_apply(params[i], grads[i], v, o);
+    vel[i] = v;
+    grads[i] = 0.f;
+  }
+}
+
 // MFMA layout self-test: D[16][16] = A[16][32] @ B[32][16], plain fp32 I/O.
 __global__ void k_mfma_selftest(const float* __restrict__ A,
                                 const float* __restrict__ Bm,
@@ -2171,6 +2238,52 @@ int pcnn_deep_update_cast(float* params, float* grads, long long n,
   hipLaunchKernelGGL(k_update_cast_all, grid, block, 0,
                      (hipStream_t)stream, params, grads, n, step,
                      (__bf16*)wbuf, d);
+  return (int)hipGetLastError();
+}
+
+// pcnn_deep_update_cast with the momentum update (k_update_cast_all_mom);
+// scale and dt are passed apart, vel is the fp32 velocity bucket [n].
+int pcnn_deep_update_cast_mom(float* params, float* grads, float* vel,
+                              long long n, float scale, float dt, float mu,
+                              float wd, int nesterov, void* wbuf,
+                              int n_stages, const int* R, const int* C,
+                              const int* K, const int* Cin,
+                              const long long* w_off, const long long* bf_off,
+                              const long long* bfT_off,
+                              const long long* rot_off,
+                              const long long* p8_off, void* stream) {
+  if (n_stages < 1 || n_stages > 8 || vel == nullptr) return -2;
+  CastDescs d;
+  d.n = n_stages;
+  d.cum[0] = 0;
+  for (int s2 = 0; s2 < n_stages; ++s2) {
+    d.R[s2] = R[s2];
+    d.C[s2] = C[s2];
+    d.K[s2] = K[s2];
+    d.Cin[s2] = Cin[s2];
+    d.w_off[s2] = w_off[s2];
+    d.bf_off[s2] = bf_off[s2];
+    d.bfT_off[s2] = bfT_off[s2];
+    d.rot_off[s2] = rot_off[s2];
+    d.p8_off[s2] = p8_off ? p8_off[s2] : -1;
+    d.cum[s2 + 1] = d.cum[s2] + (long long)R[s2] * C[s2];
+  }
+  const MomArgs o{scale, dt, mu, wd, nesterov};
+  dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  hipLaunchKernelGGL(k_update_cast_all_mom, grid, block, 0,
+                     (hipStream_t)stream, params, grads, vel, n, o,
+                     (__bf16*)wbuf, d);
+  return (int)hipGetLastError();
+}
+
+int pcnn_deep_update_mom(float* params, float* grads, float* vel, long long n,
+                         float scale, float dt, float mu, float wd,
+                         int nesterov, void* stream) {
+  if (vel == nullptr) return -2;
+  const MomArgs o{scale, dt, mu, wd, nesterov};
+  dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  hipLaunchKernelGGL(k_update_n_mom, grid, block, 0, (hipStream_t)stream,
+                     params, grads, vel, n, o);
   return (int)hipGetLastError();
 }
 

@@ -47,6 +47,11 @@
 //      SGD update.  No atomics, no gradient bucket, no ticket, no fences;
 //      results are bit-reproducible.
 //
+// Every kernel that applies the update (k_update, k_wgrad_update,
+// k_reduce_update) has a _mom twin with momentum / Nesterov / weight decay
+// and an fp32 velocity bucket (mom_apply); the plain kernels are what runs
+// when the optimizer is the default one.
+//
 // Numerics: activations AND the large conv preact gradient (dz1) are
 // stored bf16/fp16/fp32 (template); ALL arithmetic is fp32 in
 // registers/LDS; parameters, gradients, dz and dz2 are fp32.  Loss-metric
@@ -816,6 +821,81 @@ __device__ __forceinline__ void update_tail(float* __restrict__ params,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Momentum / Nesterov / weight-decay form of the update, shared by the _mom
+// variant of every update site (ascent convention, g as the plain sites
+// read it):
+//   u = scale*g - wd*p;  v = mu*v + u;  p += dt*v
+//   nesterov:            p += dt*(u + mu*v)     (v the freshly updated one)
+// v is the fp32 velocity bucket, same flat layout as params.  The plain
+// kernels are separate instantiations and never see these arguments.
+// ---------------------------------------------------------------------------
+struct MomArgs {
+  float scale, dt, mu, wd;
+  int nesterov;
+};
+
+__device__ __forceinline__ float mom_apply(float p, float g, float& v,
+                                           const MomArgs& o) {
+  const float u = o.scale * g - o.wd * p;
+  v = o.mu * v + u;
+  return p + o.dt * (o.nesterov ? u + o.mu * v : v);
+}
+
+__device__ __forceinline__ void mom_apply4(float4& p, const float4& g,
+                                           float4& v, const MomArgs& o) {
+  p.x = mom_apply(p.x, g.x, v.x, o);
+  p.y = mom_apply(p.y, g.y, v.y, o);
+  p.z = mom_apply(p.z, g.z, v.z, o);
+  p.w = mom_apply(p.w, g.w, v.w, o);
+}
+
+// update_tail with velocity: the same 585 float4 + 3-float split.  Only
+// the last-arriving block runs this, so it is the only reader and writer of
+// vel in the launch.  vel was written by the last arriver of the previous
+// launch with plain stores and has crossed a kernel boundary since, exactly
+// like params: plain loads and stores, no fences beyond the ticket's.
+__device__ __forceinline__ void update_tail_mom(float* __restrict__ params,
+                                                float* __restrict__ grads,
+                                                float* __restrict__ vel,
+                                                const MomArgs o) {
+  constexpr int NV = N_PARAMS / 4;
+  for (int i4 = threadIdx.x; i4 < NV; i4 += 256) {
+    const int i = i4 * 4;
+    float4 pv = *reinterpret_cast<float4*>(params + i);
+    float4 vv = *reinterpret_cast<float4*>(vel + i);
+    const float4 gv = *reinterpret_cast<float4*>(grads + i);
+    mom_apply4(pv, gv, vv, o);
+    *reinterpret_cast<float4*>(params + i) = pv;
+    *reinterpret_cast<float4*>(vel + i) = vv;
+    *reinterpret_cast<float4*>(grads + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  const int u = NV * 4 + threadIdx.x;
+  if (u < N_PARAMS) {
+    float v = vel[u];
+    params[u] = mom_apply(params[u], grads[u], v, o);
+    vel[u] = v;
+    grads[u] = 0.f;
+  }
+}
+
+// k_wgrad_update (below) with the momentum tail.
+template <typename act_t>
+__global__ __launch_bounds__(256) void k_wgrad_update_mom(
+    const act_t* __restrict__ x, const act_t* __restrict__ a1g,
+    const act_t* __restrict__ a2g, const float* __restrict__ dzg,
+    const float* __restrict__ dz2g, const act_t* __restrict__ dz1g,
+    float* __restrict__ grads, int B, int GC, int GS, int FS, int roles,
+    float* __restrict__ params, float* __restrict__ vel, MomArgs o,
+    int* __restrict__ ticket) {
+  wgrad_body<act_t, true>(x, a1g, a2g, dzg, dz2g, dz1g, grads, B, GC, GS,
+                          FS, roles);
+  if (!arrive_is_last(ticket)) return;
+  update_tail_mom(params, grads, vel, o);
+  if (threadIdx.x == 0)
+    __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Weight gradients with the SGD update as the tail of the same launch
 // (two-launch training step).  Gradient code is wgrad_body, unchanged; the
 // block that arrives last applies the update, zeroes the bucket and resets
@@ -861,6 +941,31 @@ __global__ __launch_bounds__(256) void k_update(float* __restrict__ params,
   }
 }
 
+// k_update with velocity (mom_apply): same float4 body + 3-float tail, vel
+// read and written as float4 alongside params.
+__global__ __launch_bounds__(256) void k_update_mom(
+    float* __restrict__ params, float* __restrict__ grads,
+    float* __restrict__ vel, MomArgs o) {
+  const int i4 = blockIdx.x * 256 + threadIdx.x;
+  const int i = i4 * 4;
+  if (i + 3 < N_PARAMS) {
+    float4 pv = *reinterpret_cast<float4*>(params + i);
+    float4 vv = *reinterpret_cast<float4*>(vel + i);
+    const float4 gv = *reinterpret_cast<float4*>(grads + i);
+    mom_apply4(pv, gv, vv, o);
+    *reinterpret_cast<float4*>(params + i) = pv;
+    *reinterpret_cast<float4*>(vel + i) = vv;
+    *reinterpret_cast<float4*>(grads + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+  } else if (i < N_PARAMS) {
+    for (int u = i; u < N_PARAMS; ++u) {
+      float v = vel[u];
+      params[u] = mom_apply(params[u], grads[u], v, o);
+      vel[u] = v;
+      grads[u] = 0.f;
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Second kernel of the in-block weight-grad step: batch-reduce + SGD apply.
 // Every parameter has exactly one owner group of RU_LANES adjacent lanes, so
@@ -884,11 +989,15 @@ constexpr int RU_BLOCKS =
 // crossover: pcnn_launch_step_inblock).
 constexpr int INBLOCK_MAX_B = 256;
 
-template <typename act_t>
-__global__ __launch_bounds__(256) void k_reduce_update(
+// MOM selects the apply at the end and nothing else: the plain kernel is the
+// MOM=false instantiation with vel and o unused, the momentum kernel has the
+// owner lane (sub == 0) do the velocity read-modify-write and the parameter
+// store after the same fixed shuffle.
+template <typename act_t, bool MOM>
+__device__ __forceinline__ void reduce_update_body(
     const float* __restrict__ gslab, const act_t* __restrict__ a2g,
     const float* __restrict__ dzg, float* __restrict__ params, float step,
-    int B) {
+    int B, float* __restrict__ vel, const MomArgs& o) {
   const int p = blockIdx.x * RU_PARAMS_PER_BLOCK + (threadIdx.x >> 2);
   const int sub = threadIdx.x & (RU_LANES - 1);
   // Lanes past the last parameter redo the last one and do not store: the
@@ -943,7 +1052,32 @@ __global__ __launch_bounds__(256) void k_reduce_update(
   }
   acc += __shfl_xor(acc, 1, RU_LANES);
   acc += __shfl_xor(acc, 2, RU_LANES);
-  if (sub == 0 && p < N_PARAMS) params[p] += step * acc;
+  if (sub == 0 && p < N_PARAMS) {
+    if constexpr (MOM) {
+      float v = vel[p];
+      params[p] = mom_apply(params[p], acc, v, o);
+      vel[p] = v;
+    } else {
+      params[p] += step * acc;
+    }
+  }
+}
+
+template <typename act_t>
+__global__ __launch_bounds__(256) void k_reduce_update(
+    const float* __restrict__ gslab, const act_t* __restrict__ a2g,
+    const float* __restrict__ dzg, float* __restrict__ params, float step,
+    int B) {
+  reduce_update_body<act_t, false>(gslab, a2g, dzg, params, step, B, nullptr,
+                                   MomArgs{});
+}
+
+template <typename act_t>
+__global__ __launch_bounds__(256) void k_reduce_update_mom(
+    const float* __restrict__ gslab, const act_t* __restrict__ a2g,
+    const float* __restrict__ dzg, float* __restrict__ params,
+    float* __restrict__ vel, MomArgs o, int B) {
+  reduce_update_body<act_t, true>(gslab, a2g, dzg, params, 0.f, B, vel, o);
 }
 
 }  // namespace pcnn
@@ -1038,7 +1172,8 @@ static int launch_wgrad_any(const void* x, const void* a1, const void* a2,
                             const void* dz1, float* grads, int B,
                             int act_is_bf16, int chunk_imgs, int roles,
                             float* params, float step, int* ticket,
-                            void* stream) {
+                            void* stream, float* vel = nullptr,
+                            const MomArgs* mom = nullptr) {
   // Batch-adaptive defaults: ~36 (image,position) items per conv thread,
   // pool slices at GC/4, fc batch slices of ~64 images.
   int GC = chunk_imgs > 0 ? chunk_imgs : (int)(4.0f * __builtin_cbrtf((float)B) + 0.5f);
@@ -1056,7 +1191,24 @@ static int launch_wgrad_any(const void* x, const void* a1, const void* a2,
   if (FS > 32) FS = 32;
   dim3 grid(C1_CH * GC + GS + FS * FC_BLOCKS), block(256);
   hipStream_t s = (hipStream_t)stream;
-  if (ticket != nullptr) {
+  if (ticket != nullptr && mom != nullptr) {
+    if (act_is_bf16 == 1) {
+      hipLaunchKernelGGL((k_wgrad_update_mom<bf16>), grid, block, 0, s,
+                         (const bf16*)x, (const bf16*)a1, (const bf16*)a2, dz,
+                         dz2, (const bf16*)dz1, grads, B, GC, GS, FS, roles,
+                         params, vel, *mom, ticket);
+    } else if (act_is_bf16 == 2) {
+      hipLaunchKernelGGL((k_wgrad_update_mom<fp16>), grid, block, 0, s,
+                         (const fp16*)x, (const fp16*)a1, (const fp16*)a2, dz,
+                         dz2, (const fp16*)dz1, grads, B, GC, GS, FS, roles,
+                         params, vel, *mom, ticket);
+    } else {
+      hipLaunchKernelGGL((k_wgrad_update_mom<float>), grid, block, 0, s,
+                         (const float*)x, (const float*)a1, (const float*)a2,
+                         dz, dz2, (const float*)dz1, grads, B, GC, GS, FS,
+                         roles, params, vel, *mom, ticket);
+    }
+  } else if (ticket != nullptr) {
     if (act_is_bf16 == 1) {
       hipLaunchKernelGGL((k_wgrad_update<bf16>), grid, block, 0, s,
                          (const bf16*)x, (const bf16*)a1, (const bf16*)a2, dz,
@@ -1238,6 +1390,102 @@ int pcnn_launch_update(float* params, float* grads, float step, void* stream) {
   hipLaunchKernelGGL(k_update, grid, block, 0, (hipStream_t)stream, params,
                      grads, step);
   return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Momentum variants of every launcher that applies the update.  scale and
+// dt are passed apart (not pre-multiplied); vel is the fp32 velocity bucket
+// [N_PARAMS].  Batch-size hand-offs mirror the plain launchers one for one,
+// so no batch size drops the optimizer state.
+// ---------------------------------------------------------------------------
+int pcnn_launch_update_mom(float* params, float* grads, float* vel,
+                           float scale, float dt, float mu, float wd,
+                           int nesterov, void* stream) {
+  if (vel == nullptr) return (int)hipErrorInvalidValue;
+  const MomArgs o{scale, dt, mu, wd, nesterov};
+  dim3 grid((N_PARAMS / 4 + 255) / 256), block(256);
+  hipLaunchKernelGGL(k_update_mom, grid, block, 0, (hipStream_t)stream,
+                     params, grads, vel, o);
+  return (int)hipGetLastError();
+}
+
+int pcnn_launch_wgrad_update_mom(const void* x, const void* a1,
+                                 const void* a2, const float* dz,
+                                 const float* dz2, const void* dz1,
+                                 float* grads, float* params, float* vel,
+                                 float scale, float dt, float mu, float wd,
+                                 int nesterov, int* ticket, int B,
+                                 int act_is_bf16, int chunk_imgs, int roles,
+                                 void* stream) {
+  if (ticket == nullptr || params == nullptr || vel == nullptr)
+    return (int)hipErrorInvalidValue;
+  const MomArgs o{scale, dt, mu, wd, nesterov};
+  if (B > 2048) {  // same kernel boundary as pcnn_launch_wgrad_update
+    const int err =
+        launch_wgrad_any(x, a1, a2, dz, dz2, dz1, grads, B, act_is_bf16,
+                         chunk_imgs, roles, nullptr, 0.f, nullptr, stream);
+    if (err != 0) return err;
+    return pcnn_launch_update_mom(params, grads, vel, scale, dt, mu, wd,
+                                  nesterov, stream);
+  }
+  return launch_wgrad_any(x, a1, a2, dz, dz2, dz1, grads, B, act_is_bf16,
+                          chunk_imgs, roles, params, 0.f, ticket, stream, vel,
+                          &o);
+}
+
+int pcnn_launch_reduce_update_mom(const float* gslab, const void* a2,
+                                  const float* dz, float* params, float* vel,
+                                  float scale, float dt, float mu, float wd,
+                                  int nesterov, int B, int act_is_bf16,
+                                  void* stream) {
+  if (gslab == nullptr || params == nullptr || vel == nullptr || B < 1)
+    return (int)hipErrorInvalidValue;
+  const MomArgs o{scale, dt, mu, wd, nesterov};
+  dim3 grid(RU_BLOCKS), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  if (act_is_bf16 == 1) {
+    hipLaunchKernelGGL((k_reduce_update_mom<bf16>), grid, block, 0, s, gslab,
+                       (const bf16*)a2, dz, params, vel, o, B);
+  } else if (act_is_bf16 == 2) {
+    hipLaunchKernelGGL((k_reduce_update_mom<fp16>), grid, block, 0, s, gslab,
+                       (const fp16*)a2, dz, params, vel, o, B);
+  } else {
+    hipLaunchKernelGGL((k_reduce_update_mom<float>), grid, block, 0, s, gslab,
+                       (const float*)a2, dz, params, vel, o, B);
+  }
+  return (int)hipGetLastError();
+}
+
+// pcnn_launch_step_inblock with the momentum update; the B > INBLOCK_MAX_B
+// hand-off goes to k_wgrad_update_mom with the same optimizer arguments.
+int pcnn_launch_step_inblock_mom(const void* x, float* params, float* vel,
+                                 void* a1, void* a2, float* y, float* dz,
+                                 float* dz2, void* dz1, const int* labels,
+                                 float* loss_accum, float* grads, int* ticket,
+                                 float* gslab, float scale, float dt,
+                                 float mu, float wd, int nesterov, int B,
+                                 int act_is_bf16, int pool_mode,
+                                 int loss_mode, int chunk_imgs,
+                                 void* stream) {
+  if (B > INBLOCK_MAX_B) {
+    int err = pcnn_launch_fwdbwd_ex2(x, params, a1, a2, y, dz, dz2, dz1,
+                                     labels, loss_accum, nullptr, B,
+                                     act_is_bf16, MODE_TRAIN, pool_mode,
+                                     loss_mode, grads, 0, stream);
+    if (err != 0) return err;
+    return pcnn_launch_wgrad_update_mom(x, a1, a2, dz, dz2, dz1, grads,
+                                        params, vel, scale, dt, mu, wd,
+                                        nesterov, ticket, B, act_is_bf16,
+                                        chunk_imgs, pool_mode == 1 ? 5 : 7,
+                                        stream);
+  }
+  int err = pcnn_launch_fwdbwd_inblock(x, params, a2, y, dz, labels,
+                                       loss_accum, gslab, B, act_is_bf16,
+                                       pool_mode, loss_mode, stream);
+  if (err != 0) return err;
+  return pcnn_launch_reduce_update_mom(gslab, a2, dz, params, vel, scale, dt,
+                                       mu, wd, nesterov, B, act_is_bf16,
+                                       stream);
 }
 
 const char* pcnn_hip_error_string(int err) {

@@ -28,6 +28,25 @@ class TrainConfig:
     grad_reduction: str = "mean"     # mean | sum over the global batch
     grad_accum: int = 1              # micro-batches per optimizer step
     threshold: float = REF_THRESHOLD  # early-stop when mean err-norm < this
+    # beyond the reference: u = scale*g - weight_decay*p; v = momentum*v + u;
+    # p += dt*v (nesterov: p += dt*(u + momentum*v)).  All zero/False keeps
+    # the plain update, with no velocity buffer
+    momentum: float = 0.0
+    weight_decay: float = 0.0
+    nesterov: bool = False
+
+    def uses_momentum(self) -> bool:
+        """True when the optimizer needs the velocity buffer; validates the
+        three optimizer fields (ValueError)."""
+        if not 0.0 <= self.momentum < 1.0:
+            raise ValueError(
+                f"momentum must be in [0, 1), got {self.momentum}")
+        if self.weight_decay < 0.0:
+            raise ValueError(
+                f"weight_decay must be >= 0, got {self.weight_decay}")
+        if self.nesterov and not self.momentum > 0.0:
+            raise ValueError("nesterov requires momentum > 0")
+        return self.momentum != 0.0 or self.weight_decay != 0.0
 
     # schedule
     epochs: int = 1                  # reference trains exactly one epoch

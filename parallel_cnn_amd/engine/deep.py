@@ -23,7 +23,7 @@ import torch
 
 from ..config import TrainConfig
 from ..models.deepcnn import DeepCNN
-from ..ops import deep_ref, native
+from ..ops import deep_ref, native, torch_ref
 from ..parallel import dist as pdist
 
 MODE_TRAIN, MODE_EVAL, MODE_INFER = 0, 1, 2
@@ -200,6 +200,12 @@ class DeepTrainer:
             spec = DeepCNNSpec(channels=channels)
             model = DeepCNN(self.device, seed=cfg.seed, spec=spec)
         self.model = model
+        # velocity of the momentum / weight-decay update: per-rank fp32
+        # state in the params layout, allocated only for a non-default
+        # optimizer (None selects the plain update everywhere)
+        self.vel: Optional[torch.Tensor] = (
+            torch.zeros_like(self.model.params) if cfg.uses_momentum()
+            else None)
         act_map = {"bf16": torch.bfloat16, "fp16": torch.float16,
                    "fp32": torch.float32}
         self.act_dtype = (act_map[cfg.act_dtype] if backend == "hip"
@@ -261,12 +267,21 @@ class DeepTrainer:
     def _hip_update(self, scale: float) -> None:
         """SGD update fused with the next step's weight cast."""
         d = self.ws.cast_desc
-        self._C.deep_update_cast(self.model.params, self.model.grads,
-                                 self.cfg.dt * scale, self.ws.wbuf, d["R"],
-                                 d["C"], d["K"], d["Cin"], d["w_off"],
-                                 d["bf_off"], d["bfT_off"], d["rot_off"],
-                                 d["p8_off"],
-                                 native.current_stream_handle())
+        if self.vel is not None:
+            c = self.cfg
+            self._C.deep_update_cast_momentum(
+                self.model.params, self.model.grads, self.vel, c.dt, scale,
+                c.momentum, c.weight_decay, c.nesterov, self.ws.wbuf,
+                d["R"], d["C"], d["K"], d["Cin"], d["w_off"], d["bf_off"],
+                d["bfT_off"], d["rot_off"], d["p8_off"],
+                native.current_stream_handle())
+        else:
+            self._C.deep_update_cast(self.model.params, self.model.grads,
+                                     self.cfg.dt * scale, self.ws.wbuf,
+                                     d["R"], d["C"], d["K"], d["Cin"],
+                                     d["w_off"], d["bf_off"], d["bfT_off"],
+                                     d["rot_off"], d["p8_off"],
+                                     native.current_stream_handle())
         self._wbuf_fresh = True
 
     def _hip_forward(self, x: torch.Tensor, labels: torch.Tensor, B: int,
@@ -535,6 +550,7 @@ class DeepTrainer:
         self._gl = torch.zeros(B, dtype=torch.int32, device=self.device)
         params0 = self.model.params.clone()
         grads0 = self.model.grads.clone()
+        vel0 = self.vel.clone() if self.vel is not None else None
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -547,6 +563,8 @@ class DeepTrainer:
         with torch.no_grad():
             self.model.params.copy_(params0)
             self.model.grads.copy_(grads0)
+            if vel0 is not None:
+                self.vel.copy_(vel0)
             self.ws.loss_accum.zero_()
             self.ws.correct_accum.zero_()
         # the captured graph contains NO cast (warmup left wbuf fresh at
@@ -610,10 +628,16 @@ class DeepTrainer:
             self.model.grads += grads
             if apply_update:
                 pdist.allreduce_grads(self.model.grads)
-                with torch.no_grad():
-                    self.model.params += (self.cfg.dt * scale *
-                                          self.model.grads)
-                    self.model.grads.zero_()
+                if self.vel is not None:
+                    c = self.cfg
+                    torch_ref.update_momentum(
+                        self.model.params, self.model.grads, self.vel, c.dt,
+                        scale, c.momentum, c.weight_decay, c.nesterov)
+                else:
+                    with torch.no_grad():
+                        self.model.params += (self.cfg.dt * scale *
+                                              self.model.grads)
+                        self.model.grads.zero_()
         self._samples_seen += B * self.ctx.world_size
         self.global_step += 1
 

@@ -13,9 +13,11 @@ Backends:
   * "torchref" — the pure-PyTorch fp32 oracle (tests/debugging).
 
 A training step is: fused fwd+bwd-data -> weight-grad -> [RCCL all-reduce of
-the flat gradient bucket] -> fused SGD update.  Loss (sum over samples of
-||onehot - y||_2, the reference's metric) accumulates device-side and is
-only synced on readout.
+the flat gradient bucket] -> fused SGD update (with momentum / Nesterov /
+weight decay and a velocity buffer when the config asks for them; the
+momentum variant of the same kernel at every update site).  Loss (sum over
+samples of ||onehot - y||_2, the reference's metric) accumulates device-side
+and is only synced on readout.
 """
 from __future__ import annotations
 
@@ -75,6 +77,12 @@ class Trainer:
         if self.backend in ("hip", "cpu"):
             self._C = native.require()
         self.model = model or LeNet5(self.device, seed=cfg.seed)
+        # velocity of the momentum / weight-decay update: per-rank fp32
+        # state in the params layout, allocated only for a non-default
+        # optimizer (None selects the plain update kernels everywhere)
+        self.vel: Optional[torch.Tensor] = (
+            torch.zeros_like(self.model.params) if cfg.uses_momentum()
+            else None)
         act_map = {"bf16": torch.bfloat16, "fp16": torch.float16,
                    "fp32": torch.float32}
         act_dtype = (act_map[cfg.act_dtype] if self.backend == "hip"
@@ -136,6 +144,13 @@ class Trainer:
     def _step_inblock(self, x: torch.Tensor, labels: torch.Tensor, B: int,
                       stream: int) -> None:
         m, w = self.model, self.ws
+        if self.vel is not None:
+            self._C.hip_step_inblock_momentum(
+                x, m.params, self.vel, w.a1, w.a2, w.y, w.dz, w.dz2, w.dz1,
+                labels, w.loss_accum, m.grads, w.ticket, w.gslab,
+                *self._opt_args(B), B, self.cfg.wgrad_chunk, stream,
+                self._pool_mode, self._loss_mode)
+            return
         self._C.hip_step_inblock(x, m.params, w.a1, w.a2, w.y, w.dz, w.dz2,
                                  w.dz1, labels, w.loss_accum, m.grads,
                                  w.ticket, w.gslab,
@@ -149,6 +164,38 @@ class Trainer:
             return 1.0 / float(local_batch * self.ctx.world_size *
                                self.cfg.grad_accum)
         return 1.0
+
+    def _opt_args(self, local_batch: int):
+        """(dt, scale, mu, wd, nesterov) as every momentum binding takes
+        them, after vel."""
+        c = self.cfg
+        return (c.dt, self._update_scale(local_batch), c.momentum,
+                c.weight_decay, c.nesterov)
+
+    def _hip_apply_update(self, B: int, stream: int) -> None:
+        """The stand-alone update launch of the 3-launch step."""
+        m = self.model
+        if self.vel is not None:
+            self._C.hip_update_momentum(m.params, m.grads, self.vel,
+                                        *self._opt_args(B), stream)
+        else:
+            self._C.hip_update(m.params, m.grads,
+                               self.cfg.dt * self._update_scale(B), stream)
+
+    def _hip_wgrad_update(self, x: torch.Tensor, B: int, stream: int) -> None:
+        """Weight grads with the update as the tail of the same launch."""
+        m, w = self.model, self.ws
+        if self.vel is not None:
+            self._C.hip_wgrad_update_momentum(
+                x, w.a1, w.a2, w.dz, w.dz2, w.dz1, m.grads, m.params,
+                self.vel, *self._opt_args(B), w.ticket, B,
+                self.cfg.wgrad_chunk, self._wroles, stream)
+        else:
+            self._C.hip_wgrad_update(x, w.a1, w.a2, w.dz, w.dz2, w.dz1,
+                                     m.grads, m.params,
+                                     self.cfg.dt * self._update_scale(B),
+                                     w.ticket, B, self.cfg.wgrad_chunk,
+                                     self._wroles, stream)
 
     def stage_batch(self, x: torch.Tensor, labels: torch.Tensor
                     ) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -194,11 +241,7 @@ class Trainer:
                                B, MODE_TRAIN, stream, self._pool_mode,
                                self._loss_mode, m.grads, self._fuse)
             if self._fused_step_mode() == 2:
-                self._C.hip_wgrad_update(x, w.a1, w.a2, w.dz, w.dz2, w.dz1,
-                                         m.grads, m.params,
-                                         self.cfg.dt * scale, w.ticket, B,
-                                         self.cfg.wgrad_chunk, self._wroles,
-                                         stream)
+                self._hip_wgrad_update(x, B, stream)
                 apply_update = False  # done in the wgrad launch
             elif not apply_update:
                 self._C.hip_wgrad_roles(x, w.a1, w.a2, w.dz, w.dz2, w.dz1,
@@ -239,8 +282,7 @@ class Trainer:
                                         self._wroles, stream)
                 pdist.allreduce_grads(m.grads)
             if apply_update:
-                self._C.hip_update(m.params, m.grads, self.cfg.dt * scale,
-                                   stream)
+                self._hip_apply_update(B, stream)
         elif self.backend == "cpu":
             # CPU path keeps fp32 activations in the workspace directly.
             a1 = self._cpu_view(w.a1, B)
@@ -254,7 +296,11 @@ class Trainer:
             self._loss_host += loss
             if apply_update:
                 pdist.allreduce_grads(m.grads)
-                self._C.cpu_update(m.params, m.grads, self.cfg.dt, scale)
+                if self.vel is not None:
+                    self._C.cpu_update_momentum(m.params, m.grads, self.vel,
+                                                *self._opt_args(B))
+                else:
+                    self._C.cpu_update(m.params, m.grads, self.cfg.dt, scale)
         else:  # torchref
             a1, a2, y = torch_ref.forward(x, m.params, self.cfg.pool,
                                           self.cfg.loss)
@@ -264,14 +310,17 @@ class Trainer:
             m.grads += grads
             if apply_update:
                 pdist.allreduce_grads(m.grads)
-                torch_ref.update(m.params, m.grads, self.cfg.dt, scale)
+                if self.vel is not None:
+                    torch_ref.update_momentum(m.params, m.grads, self.vel,
+                                              *self._opt_args(B))
+                else:
+                    torch_ref.update(m.params, m.grads, self.cfg.dt, scale)
         self._samples_seen += B * self.ctx.world_size
         self.global_step += 1
 
     def _step_profiled(self, x: torch.Tensor, labels: torch.Tensor) -> None:
         B = x.shape[0]
         m, w, t = self.model, self.ws, self.timers
-        scale = self._update_scale(B)
         if self.backend != "hip":
             with t.phase("step"):
                 self.timers = None
@@ -293,8 +342,7 @@ class Trainer:
         with t.phase("all-reduce"):
             pdist.allreduce_grads(m.grads)
         with t.phase("update"):
-            self._C.hip_update(m.params, m.grads, self.cfg.dt * scale,
-                               stream)
+            self._hip_apply_update(B, stream)
         self._samples_seen += B * self.ctx.world_size
         self.global_step += 1
 
@@ -319,6 +367,7 @@ class Trainer:
         # steps, so snapshot and restore the training state around it
         params0 = self.model.params.clone()
         grads0 = self.model.grads.clone()
+        vel0 = self.vel.clone() if self.vel is not None else None
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -331,6 +380,8 @@ class Trainer:
         with torch.no_grad():
             self.model.params.copy_(params0)
             self.model.grads.copy_(grads0)
+            if vel0 is not None:
+                self.vel.copy_(vel0)
             self.ws.loss_accum.zero_()
         torch.cuda.synchronize()
 
@@ -345,19 +396,13 @@ class Trainer:
                            B, MODE_TRAIN, stream, self._pool_mode,
                            self._loss_mode, m.grads, self._fuse)
         if self._fused_step_mode() == 2:
-            self._C.hip_wgrad_update(self._gx, w.a1, w.a2, w.dz, w.dz2,
-                                     w.dz1, m.grads, m.params,
-                                     self.cfg.dt * self._update_scale(B),
-                                     w.ticket, B, self.cfg.wgrad_chunk,
-                                     self._wroles, stream)
+            self._hip_wgrad_update(self._gx, B, stream)
             return
         self._C.hip_wgrad_roles(self._gx, w.a1, w.a2, w.dz, w.dz2, w.dz1,
                                 m.grads, B, self.cfg.wgrad_chunk,
                                 self._wroles, stream)
         pdist.allreduce_grads(m.grads)
-        self._C.hip_update(m.params, m.grads,
-                           self.cfg.dt * self._update_scale(B),
-                           native.current_stream_handle())
+        self._hip_apply_update(B, native.current_stream_handle())
 
     def step_graph(self, x: torch.Tensor, labels: torch.Tensor) -> None:
         """Replay the captured step on a staged batch (one D2D copy in)."""
@@ -382,6 +427,11 @@ class Trainer:
             return
         if self.backend == "hip" and not pdist.is_distributed():
             w = self.ws
+            opt = {}
+            if self.vel is not None:
+                dt, scale, mu, wd, nesterov = self._opt_args(B)
+                opt = dict(vel=self.vel, dt=dt, scale=scale, mu=mu, wd=wd,
+                           nesterov=nesterov)
             self._C.hip_train_steps(
                 x_pool, labels_pool, self.model.params, self.model.grads,
                 w.a1, w.a2, w.y, w.dz, w.dz2, w.dz1, w.loss_accum, B, steps,
@@ -389,7 +439,7 @@ class Trainer:
                 native.current_stream_handle(), self._pool_mode,
                 self._loss_mode, self._fuse,
                 4 if self._use_inblock() else self._fused_step_mode(),
-                w.ticket, w.gslab)
+                w.ticket, w.gslab, **opt)
             self._samples_seen += B * steps
             self.global_step += steps
         else:

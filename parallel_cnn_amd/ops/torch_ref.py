@@ -132,3 +132,16 @@ def update(params: torch.Tensor, grads: torch.Tensor, dt: float,
            scale: float) -> None:
     params += dt * scale * grads
     grads.zero_()
+
+
+def update_momentum(params: torch.Tensor, grads: torch.Tensor,
+                    vel: torch.Tensor, dt: float, scale: float, mu: float,
+                    wd: float, nesterov: bool) -> None:
+    """Momentum / Nesterov / weight decay in the ascent convention, i.e.
+    torch.optim.SGD(lr=dt, momentum=mu, weight_decay=wd, nesterov=nesterov)
+    fed grad = -scale*grads.  In place on params and vel; zeroes grads."""
+    with torch.no_grad():
+        u = scale * grads - wd * params
+        vel.mul_(mu).add_(u)
+        params += dt * (u + mu * vel if nesterov else vel)
+        grads.zero_()

@@ -1,7 +1,8 @@
 """Checkpoint/resume: flat LE fp32 weights (the parity format)
 plus a JSON sidecar with training state for EXACT resume (global step,
 epoch cursor, host/device RNG states — so train(2N epochs) ==
-train(N) -> save -> load -> train(N))."""
+train(N) -> save -> load -> train(N)).  A non-default optimizer (momentum
+or weight decay) adds its velocity as flat LE fp32 at `path + '.vel'`."""
 from __future__ import annotations
 
 import base64
@@ -47,8 +48,40 @@ def save_checkpoint(trainer, path: str) -> None:
         "n_params": int(trainer.model.params.numel()),
         "rng": _rng_capture(),
     }
+    vel = getattr(trainer, "vel", None)
+    if vel is not None:
+        # non-default optimizer only: the default writes exactly the files
+        # and keys it always wrote
+        vel.detach().cpu().numpy().astype("<f4").tofile(path + ".vel")
+        meta["momentum"] = trainer.cfg.momentum
+        meta["weight_decay"] = trainer.cfg.weight_decay
+        meta["nesterov"] = trainer.cfg.nesterov
     with open(path + ".meta.json", "w") as f:
         json.dump(meta, f, indent=1)
+
+
+def _load_velocity(trainer, path: str) -> None:
+    """Restore trainer.vel from `path + '.vel'`: a size mismatch raises; a
+    missing file under momentum > 0 starts from zero with a warning."""
+    vel = getattr(trainer, "vel", None)
+    if vel is None:
+        return
+    vel_path = path + ".vel"
+    if not os.path.exists(vel_path):
+        if trainer.cfg.momentum > 0:
+            print(f"warning: checkpoint {path!r} has no velocity file; "
+                  f"momentum restarts from zero velocity")
+        with torch.no_grad():
+            vel.zero_()
+        return
+    import numpy as np
+    arr = np.fromfile(vel_path, dtype="<f4")
+    if arr.size != vel.numel():
+        raise ValueError(
+            f"velocity file {vel_path!r} has {arr.size} floats, "
+            f"expected {vel.numel()}")
+    with torch.no_grad():
+        vel.copy_(torch.from_numpy(arr.copy()).to(vel.device))
 
 
 def load_checkpoint(trainer, path: str) -> Optional[dict]:
@@ -57,6 +90,7 @@ def load_checkpoint(trainer, path: str) -> Optional[dict]:
     trainer.model.load(path)
     if hasattr(trainer, "invalidate_weight_cache"):
         trainer.invalidate_weight_cache()
+    _load_velocity(trainer, path)
     meta_path = path + ".meta.json"
     if not os.path.exists(meta_path):
         return None
