@@ -62,6 +62,29 @@ int pcnn_launch_reduce_update(const float* gslab, const void* a2,
                               const float* dz, float* params, float step,
                               int B, int act_is_bf16, void* stream);
 int pcnn_inblock_max_batch();
+// _v launchers: variant 0 = cell kernel, 1 = pair kernel, -1 = default
+int pcnn_inblock_default_variant();
+int pcnn_launch_fwdbwd_inblock_v(const void* x, const float* params, void* a2,
+                                 float* y, float* dz, const int* labels,
+                                 float* loss_accum, float* gslab, int B,
+                                 int act_is_bf16, int pool_mode,
+                                 int loss_mode, int variant, void* stream);
+int pcnn_launch_step_inblock_v(const void* x, float* params, void* a1,
+                               void* a2, float* y, float* dz, float* dz2,
+                               void* dz1, const int* labels,
+                               float* loss_accum, float* grads, int* ticket,
+                               float* gslab, float step, int B,
+                               int act_is_bf16, int pool_mode, int loss_mode,
+                               int chunk_imgs, int variant, void* stream);
+int pcnn_launch_step_inblock_mom_v(const void* x, float* params, float* vel,
+                                   void* a1, void* a2, float* y, float* dz,
+                                   float* dz2, void* dz1, const int* labels,
+                                   float* loss_accum, float* grads,
+                                   int* ticket, float* gslab, float scale,
+                                   float dt, float mu, float wd, int nesterov,
+                                   int B, int act_is_bf16, int pool_mode,
+                                   int loss_mode, int chunk_imgs, int variant,
+                                   void* stream);
 int pcnn_launch_step_inblock(const void* x, float* params, void* a1, void* a2,
                              float* y, float* dz, float* dz2, void* dz1,
                              const int* labels, float* loss_accum,
@@ -355,6 +378,14 @@ float* gslab_ptr(const at::Tensor& gslab, int64_t B) {
   return gslab.data_ptr<float>();
 }
 
+// Kernel 1 of the in-block step: 0 = cell (k_fwdbwd<.., INBLOCK>), 1 = pair
+// (k_fwdbwd_pair), -1 = the library default (_C.INBLOCK_DEFAULT_VARIANT).
+int inblock_variant(int64_t variant) {
+  TORCH_CHECK(variant >= -1 && variant <= 1,
+              "variant must be -1 (default), 0 (cell) or 1 (pair)");
+  return (int)variant;
+}
+
 // First kernel of the in-block weight-grad step on its own: forward +
 // backward-data in train mode, with this batch's conv/pool gradient sums
 // written to rows [0, B) of gslab.  a1, dz1 and dz2 are not produced.
@@ -362,7 +393,7 @@ void hip_fwdbwd_inblock(at::Tensor x, at::Tensor params, at::Tensor a2,
                         at::Tensor y, at::Tensor dz, at::Tensor labels,
                         at::Tensor loss_accum, at::Tensor gslab, int64_t B,
                         int64_t stream, int64_t pool_mode,
-                        int64_t loss_mode) {
+                        int64_t loss_mode, int64_t variant) {
   TORCH_CHECK(x.is_cuda() && params.is_cuda(), "expected device tensors");
   TORCH_CHECK(labels.scalar_type() == at::kInt, "labels must be int32");
   TORCH_CHECK(B >= 1 && x.numel() >= B * pcnn::IN_PIX &&
@@ -371,13 +402,13 @@ void hip_fwdbwd_inblock(at::Tensor x, at::Tensor params, at::Tensor a2,
                   y.numel() >= B * pcnn::FC_OUT &&
                   dz.numel() >= B * pcnn::FC_OUT && labels.numel() >= B,
               "buffers too small for B");
-  check_hip(pcnn_launch_fwdbwd_inblock(
+  check_hip(pcnn_launch_fwdbwd_inblock_v(
                 x.data_ptr(), params.data_ptr<float>(), a2.data_ptr(),
                 y.data_ptr<float>(), dz.data_ptr<float>(),
                 labels.data_ptr<int>(),
                 loss_accum.numel() ? loss_accum.data_ptr<float>() : nullptr,
                 gslab_ptr(gslab, B), (int)B, act_flag(x), (int)pool_mode,
-                (int)loss_mode, (void*)stream),
+                (int)loss_mode, inblock_variant(variant), (void*)stream),
             "fwdbwd_inblock");
 }
 
@@ -390,7 +421,8 @@ void hip_step_inblock(at::Tensor x, at::Tensor params, at::Tensor a1,
                       at::Tensor loss_accum, at::Tensor grads,
                       at::Tensor ticket, at::Tensor gslab, double step,
                       int64_t B, int64_t chunk_imgs, int64_t stream,
-                      int64_t pool_mode, int64_t loss_mode) {
+                      int64_t pool_mode, int64_t loss_mode,
+                      int64_t variant) {
   TORCH_CHECK(x.is_cuda() && params.is_cuda(), "expected device tensors");
   TORCH_CHECK(labels.scalar_type() == at::kInt, "labels must be int32");
   TORCH_CHECK(dz1.scalar_type() == x.scalar_type() &&
@@ -409,14 +441,14 @@ void hip_step_inblock(at::Tensor x, at::Tensor params, at::Tensor a1,
                    dz1.numel() >= B * pcnn::C1_OUT &&
                    dz2.numel() >= B * pcnn::S1_OUT),
               "a1/dz1/dz2 too small for the large-batch path");
-  check_hip(pcnn_launch_step_inblock(
+  check_hip(pcnn_launch_step_inblock_v(
                 x.data_ptr(), params.data_ptr<float>(), a1.data_ptr(),
                 a2.data_ptr(), y.data_ptr<float>(), dz.data_ptr<float>(),
                 dz2.data_ptr<float>(), dz1.data_ptr(), labels.data_ptr<int>(),
                 loss_accum.data_ptr<float>(), grads.data_ptr<float>(),
                 ticket_ptr(ticket), gslab_ptr(gslab, B), (float)step, (int)B,
                 act_flag(x), (int)pool_mode, (int)loss_mode, (int)chunk_imgs,
-                (void*)stream),
+                inblock_variant(variant), (void*)stream),
             "step_inblock");
 }
 
@@ -454,7 +486,7 @@ void hip_step_inblock_momentum(at::Tensor x, at::Tensor params,
                                double scale, double mu, double wd,
                                bool nesterov, int64_t B, int64_t chunk_imgs,
                                int64_t stream, int64_t pool_mode,
-                               int64_t loss_mode) {
+                               int64_t loss_mode, int64_t variant) {
   TORCH_CHECK(x.is_cuda() && params.is_cuda(), "expected device tensors");
   TORCH_CHECK(labels.scalar_type() == at::kInt, "labels must be int32");
   TORCH_CHECK(dz1.scalar_type() == x.scalar_type() &&
@@ -473,7 +505,7 @@ void hip_step_inblock_momentum(at::Tensor x, at::Tensor params,
                    dz1.numel() >= B * pcnn::C1_OUT &&
                    dz2.numel() >= B * pcnn::S1_OUT),
               "a1/dz1/dz2 too small for the large-batch path");
-  check_hip(pcnn_launch_step_inblock_mom(
+  check_hip(pcnn_launch_step_inblock_mom_v(
                 x.data_ptr(), params.data_ptr<float>(), vel_ptr(vel, params),
                 a1.data_ptr(), a2.data_ptr(), y.data_ptr<float>(),
                 dz.data_ptr<float>(), dz2.data_ptr<float>(), dz1.data_ptr(),
@@ -482,7 +514,7 @@ void hip_step_inblock_momentum(at::Tensor x, at::Tensor params,
                 gslab_ptr(gslab, B), (float)scale, (float)dt, (float)mu,
                 (float)wd, nesterov ? 1 : 0, (int)B, act_flag(x),
                 (int)pool_mode, (int)loss_mode, (int)chunk_imgs,
-                (void*)stream),
+                inblock_variant(variant), (void*)stream),
             "step_inblock_momentum");
 }
 
@@ -503,7 +535,9 @@ void hip_train_steps(at::Tensor x_pool, at::Tensor labels_pool,
                      int64_t loss_mode, int64_t wgrad_fuse,
                      int64_t step_mode, at::Tensor ticket,
                      at::Tensor gslab, at::Tensor vel, double dt,
-                     double scale, double mu, double wd, bool nesterov) {
+                     double scale, double mu, double wd, bool nesterov,
+                     int64_t variant) {
+  const int var = inblock_variant(variant);
   // a non-empty vel selects the momentum update in every step mode; dt and
   // scale then replace the pre-multiplied step_scale
   float* vp = vel.numel() ? vel_ptr(vel, params) : nullptr;
@@ -537,23 +571,23 @@ void hip_train_steps(at::Tensor x_pool, at::Tensor labels_pool,
     const void* xb = xp + (size_t)i * B * pcnn::IN_PIX * esz;
     const int* lb = lp + i * B;
     if (slab != nullptr && vp != nullptr) {
-      check_hip(pcnn_launch_step_inblock_mom(
+      check_hip(pcnn_launch_step_inblock_mom_v(
                     xb, pp, vp, a1.data_ptr(), a2.data_ptr(),
                     y.data_ptr<float>(), dz.data_ptr<float>(),
                     dz2.data_ptr<float>(), dz1.data_ptr(), lb,
                     loss_accum.data_ptr<float>(), gp, tk, slab, o_scale,
                     o_dt, o_mu, o_wd, o_nes, (int)B, f, (int)pool_mode,
-                    (int)loss_mode, (int)chunk_imgs, s),
+                    (int)loss_mode, (int)chunk_imgs, var, s),
                 "train_steps/step_inblock_momentum");
       continue;
     }
     if (slab != nullptr) {
-      check_hip(pcnn_launch_step_inblock(
+      check_hip(pcnn_launch_step_inblock_v(
                     xb, pp, a1.data_ptr(), a2.data_ptr(), y.data_ptr<float>(),
                     dz.data_ptr<float>(), dz2.data_ptr<float>(),
                     dz1.data_ptr(), lb, loss_accum.data_ptr<float>(), gp, tk,
                     slab, (float)step_scale, (int)B, f, (int)pool_mode,
-                    (int)loss_mode, (int)chunk_imgs, s),
+                    (int)loss_mode, (int)chunk_imgs, var, s),
                 "train_steps/step_inblock");
       continue;
     }
@@ -986,7 +1020,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("step_mode") = 3, py::arg("ticket") = at::empty({0}),
         py::arg("gslab") = at::empty({0}), py::arg("vel") = at::empty({0}),
         py::arg("dt") = 0.0, py::arg("scale") = 1.0, py::arg("mu") = 0.0,
-        py::arg("wd") = 0.0, py::arg("nesterov") = false);
+        py::arg("wd") = 0.0, py::arg("nesterov") = false,
+        py::arg("variant") = -1);
   m.def("hip_update_momentum", &hip_update_momentum, py::arg("params"),
         py::arg("grads"), py::arg("vel"), py::arg("dt"), py::arg("scale"),
         py::arg("mu"), py::arg("wd"), py::arg("nesterov"),
@@ -1008,19 +1043,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("grads"), py::arg("ticket"), py::arg("gslab"), py::arg("dt"),
         py::arg("scale"), py::arg("mu"), py::arg("wd"), py::arg("nesterov"),
         py::arg("B"), py::arg("chunk_imgs"), py::arg("stream"),
-        py::arg("pool_mode") = 0, py::arg("loss_mode") = 0);
+        py::arg("pool_mode") = 0, py::arg("loss_mode") = 0,
+        py::arg("variant") = -1);
   m.def("hip_fwdbwd_inblock", &hip_fwdbwd_inblock, py::arg("x"),
         py::arg("params"), py::arg("a2"), py::arg("y"), py::arg("dz"),
         py::arg("labels"), py::arg("loss_accum"), py::arg("gslab"),
         py::arg("B"), py::arg("stream"), py::arg("pool_mode") = 0,
-        py::arg("loss_mode") = 0);
+        py::arg("loss_mode") = 0, py::arg("variant") = -1);
   m.def("hip_step_inblock", &hip_step_inblock, py::arg("x"),
         py::arg("params"), py::arg("a1"), py::arg("a2"), py::arg("y"),
         py::arg("dz"), py::arg("dz2"), py::arg("dz1"), py::arg("labels"),
         py::arg("loss_accum"), py::arg("grads"), py::arg("ticket"),
         py::arg("gslab"), py::arg("step"), py::arg("B"),
         py::arg("chunk_imgs"), py::arg("stream"), py::arg("pool_mode") = 0,
-        py::arg("loss_mode") = 0);
+        py::arg("loss_mode") = 0, py::arg("variant") = -1);
   m.def("hip_wgrad_update", &hip_wgrad_update, py::arg("x"), py::arg("a1"),
         py::arg("a2"), py::arg("dz"), py::arg("dz2"), py::arg("dz1"),
         py::arg("grads"), py::arg("params"), py::arg("step"),
@@ -1070,6 +1106,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("N_PARAMS") = pcnn::N_PARAMS;
   m.attr("GSLAB_LD") = pcnn::GSLAB_LD;
   m.attr("INBLOCK_MAX_BATCH") = pcnn_inblock_max_batch();
+  m.attr("INBLOCK_DEFAULT_VARIANT") = pcnn_inblock_default_variant();
   m.attr("OFF_C1W") = pcnn::OFF_C1W;
   m.attr("OFF_C1B") = pcnn::OFF_C1B;
   m.attr("OFF_S1W") = pcnn::OFF_S1W;

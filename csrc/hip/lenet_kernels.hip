@@ -47,6 +47,15 @@
 //      SGD update.  No atomics, no gradient bucket, no ticket, no fences;
 //      results are bit-reproducible.
 //
+// k_fwdbwd_pair is kernel 1 of that step with two adjacent lanes per pool
+// cell and 512-thread blocks (two waves per SIMD), every global load issued
+// before the first FMA, pair-reduced weight-grad partials and a wider owner
+// split; it is what the step launchers run by default
+// (INBLOCK_DEFAULT_VARIANT; 10.05 against 13.80 us/step at bs=64,
+// profiles/r6).  k_fwdbwd<.., INBLOCK> stays selectable (variant 0) and
+// still serves nothing else differently: TRAIN, EVAL, INFER and wgrad_fuse
+// are the template as before.
+//
 // Every kernel that applies the update (k_update, k_wgrad_update,
 // k_reduce_update) has a _mom twin with momentum / Nesterov / weight decay
 // and an fp32 velocity bucket (mom_apply); the plain kernels are what runs
@@ -58,7 +67,8 @@
 // semantics match the reference (sum over samples of ||onehot - y||_2,
 // SURVEY.md §0.1 item 3).
 //
-// Wave width is 64 (CDNA4); block size 256 = 4 waves.
+// Wave width is 64 (CDNA4); block size 256 = 4 waves (k_fwdbwd_pair: 512 =
+// 8 waves).
 
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
@@ -164,6 +174,61 @@ __device__ __forceinline__ float* inblock_rows() {
   return rows;
 }
 
+// Phase stamps (diagnostic build only, -DPCNN_LENET_STAMPS; tools/
+// phase_stamps.py).  Lane 0 of every wave stores the shader clock at fixed
+// points of the two in-block training kernels into a side buffer of its
+// own, [blocks][512][ST_N] 64-bit words indexed by thread so the store is
+// an ordinary per-lane one.  In the shipped extension the macros are empty
+// and no kernel changes.
+#ifdef PCNN_LENET_STAMPS
+constexpr int ST_N = 16;
+__device__ unsigned long long* g_stamps = nullptr;
+__device__ int g_stamp_blocks = 0;
+#define PCNN_STAMP(i)                                                        \
+  do {                                                                       \
+    __builtin_amdgcn_sched_barrier(0);                                       \
+    if ((threadIdx.x & 63) == 0 && (int)blockIdx.x < g_stamp_blocks)         \
+      g_stamps[((size_t)blockIdx.x * 512 + threadIdx.x) * ST_N + (i)] =      \
+          __builtin_amdgcn_s_memtime();                                      \
+    __builtin_amdgcn_sched_barrier(0);                                       \
+  } while (0)
+#define PCNN_STAMP_DRAIN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#define PCNN_STAMP_LDS_DRAIN() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+#else
+#define PCNN_STAMP(i) ((void)0)
+#define PCNN_STAMP_DRAIN() ((void)0)
+#define PCNN_STAMP_LDS_DRAIN() ((void)0)
+#endif
+// Stamp points, the same in k_fwdbwd<INBLOCK> and k_fwdbwd_pair.
+enum {
+  ST_ENTRY = 0,     // kernel entry
+  ST_LOADS = 1,     // input window (pair: and every hoisted load) landed
+  ST_CONV = 2,      // conv + pool FMAs and sigmoids done
+  ST_BAR1 = 3,      // past barrier 1
+  ST_FC = 4,        // fc forward + residual done
+  ST_BAR2 = 5,      // past barrier 2 (and the softmax tail)
+  ST_BWD = 6,       // fc backward + pool backward done
+  ST_WGRAD = 7,     // weight-grad FMAs done
+  ST_LDS = 8,       // partials stored to LDS
+  ST_BAR3 = 9,      // past barrier 3
+  ST_OWNER = 10,    // owner sums done
+  ST_END = 11       // last global store drained
+};
+
+// Inside the k_fwdbwd template only the INBLOCK instantiations are stamped.
+#define IB_STAMP(i)                      \
+  do {                                   \
+    if constexpr (INBLOCK) PCNN_STAMP(i); \
+  } while (0)
+#define IB_STAMP_DRAIN()                        \
+  do {                                          \
+    if constexpr (INBLOCK) PCNN_STAMP_DRAIN();   \
+  } while (0)
+#define IB_STAMP_LDS_DRAIN()                        \
+  do {                                              \
+    if constexpr (INBLOCK) PCNN_STAMP_LDS_DRAIN();   \
+  } while (0)
+
 // Fused forward + backward-data, one 256-thread workgroup per image.
 //
 // Dataflow: thread t < 216 OWNS pool cell (o, pr, pc) — it computes the
@@ -193,6 +258,7 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
   const int b = blockIdx.x;
   if (b >= B) return;
   const int tid = threadIdx.x;
+  IB_STAMP(ST_ENTRY);
 
   // No staging phase: each thread loads its own 8x8 input window straight
   // from global (overlapping windows hit L1; one 1.5 KB image per block)
@@ -224,6 +290,8 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
              &xw[u][v4 * 4]);
     const float* w = params + OFF_C1W + o * C1_K * C1_K;
     const float cb = params[OFF_C1B + o];
+    IB_STAMP_DRAIN();
+    IB_STAMP(ST_LOADS);
     // pool preact: trainable weighted sum (reference) or max
     float pacc = pool_mode == 1 ? -1e30f : params[OFF_S1B];
 #pragma unroll
@@ -255,8 +323,10 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
     a2v = sigmoidf_dev(pacc);
     L.a2s[tid] = a2v;
     if (MODE == MODE_TRAIN) stf(a2g + (size_t)b * S1_OUT + tid, a2v);
+    IB_STAMP(ST_CONV);
   }
   __syncthreads();
+  IB_STAMP(ST_BAR1);
 
   // ---- phase 2: fc (216 -> 10) + sigmoid [+ loss residual] ----
   // 16 lanes per output class, 4-step shuffle tree; the group leader
@@ -289,6 +359,7 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
         }
       }
     }
+    IB_STAMP(ST_FC);
   }
   __syncthreads();
   if (loss_mode == 1) {
@@ -335,6 +406,7 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
   if (MODE == MODE_INFER) return;
 
   // ---- phase 3: fc bwd -> pool preact grad -> pool bwd (no barriers) ----
+  IB_STAMP(ST_BAR2);
   if (tid < S1_OUT) {
     float da = 0.f;
 #pragma unroll
@@ -371,6 +443,7 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
                  (pr * S1_K + i) * C1_W + pc * S1_K,
              &dz1v[i * S1_K]);
     }
+    IB_STAMP(ST_BWD);
     if constexpr (INBLOCK) {
       // conv1 partial of this cell: 16 dz1 x the 8x8 window, all registers
       // (400 FMAs, no loads); pool partial: d2 x the cell's 16 activations.
@@ -396,6 +469,7 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
             for (int v = 0; v < C1_K; ++v)
               cacc[u * C1_K + v] += d * xw[i + u][j + v];
         }
+      IB_STAMP(ST_WGRAD);
       float* row = inblock_rows() + tid * IB_LD;
 #pragma unroll
       for (int w2 = 0; w2 < C1_K * C1_K; ++w2) row[w2] = cacc[w2];
@@ -406,6 +480,8 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
           row[IB_CONV + t] = d2 * (float)(act_t)a1v[t];
         row[IB_CONV + S1_WSZ] = d2;
       }
+      IB_STAMP_LDS_DRAIN();
+      IB_STAMP(ST_LDS);
     } else if (wgrad_fuse) {
       // conv1 wgrad: this cell's 16 dz1 x its 8x8 input window (from LDS);
       // per-thread register accumulation, LDS-atomic combine per channel,
@@ -450,6 +526,7 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
   }
   if constexpr (INBLOCK) {
     __syncthreads();
+    IB_STAMP(ST_BAR3);
     // Owners sum the 216 rows in a fixed order and store this image's slab
     // row with plain stores; the kernel boundary publishes them.
     const float* rows = inblock_rows();
@@ -468,6 +545,7 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
         s3 += col[(c + 3) * IB_LD];
       }
       const float v = ((s0 + s1) + (s2 + s3)) * (1.0f / (float)C1_PIX);
+      IB_STAMP(ST_OWNER);
       out[w2 < C1_K * C1_K ? OFF_C1W + o2 * C1_K * C1_K + w2 : OFF_C1B + o2] =
           v;
     } else if (tid >= IB_POOL_T0 && tid < IB_POOL_T0 + 4 * (S1_WSZ + 1)) {
@@ -489,9 +567,12 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
       }
       s += __shfl_xor(s, 1, 4);
       s += __shfl_xor(s, 2, 4);
+      IB_STAMP(ST_OWNER);
       if (part == 0)
         out[OFF_S1W + w2] = w2 < S1_WSZ ? s : s * (1.0f / (float)S1_OUT);
     }
+    IB_STAMP_DRAIN();
+    IB_STAMP(ST_END);
   } else if (MODE == MODE_TRAIN && wgrad_fuse) {
     __syncthreads();
     // conv grads carry the reference 1/(24*24) factor; pool bias /216
@@ -513,6 +594,366 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
         unsafeAtomicAdd(&grads[OFF_S1B], L.gs1[S1_WSZ] / (float)S1_OUT);
     }
   }
+}
+
+// ---------------------------------------------------------------------------
+// k_fwdbwd_pair: the in-block training kernel (k_fwdbwd<.., TRAIN, INBLOCK>)
+// with TWO adjacent lanes per pool cell and 512-thread blocks, so every SIMD
+// holds two waves and the FMA stream issues at the two-wave rate.
+//
+//   * lane h of a pair computes conv rows 2h, 2h+1 of the cell (8 outputs
+//     over a 6x8 window).  Each conv output keeps the cell kernel's FMA
+//     order; the pool pre-activation keeps its left-to-right order too: lane
+//     0 runs its 8 terms from the bias, hands the running sum to lane 1,
+//     which continues with its 8.  a2, y, dz and the loss terms are
+//     therefore bit-identical to the cell kernel's.
+//   * every load whose address is known at entry is issued before the first
+//     conv FMA and held in registers: the fc row slice of the phase-2 lanes,
+//     the fc column of the cell, the fc bias, labels[b], the pool weights
+//     and bias, the conv weights and bias.  Phase 1 is branch-free (lanes
+//     past the last cell redo the last cell and store nothing) and a
+//     scheduling barrier closes the load block, so nothing can sink a load
+//     below the FMAs; they are consumed once before barrier 1.
+//   * conv weight-grad partials are combined across the pair with one
+//     xor-1 add per value (both lanes then hold the same sum); each lane
+//     stores half of the row: 13 conv sums + its own 8 pool products
+//     (+ d2 from lane 1), PR_HALF words per lane at address tid * PR_HALF,
+//     an odd stride, so the stores are conflict-free.
+//   * owners: two lanes per conv sum (18 cells each), eight per pool sum
+//     (27 cells each), fixed order, fixed xor tree.  The slab row differs
+//     from the cell kernel's only in summation order.
+// ---------------------------------------------------------------------------
+constexpr int PR_THREADS = 512;
+constexpr int PR_ACTIVE = 2 * S1_OUT;      // 432 lanes own half a cell
+constexpr int PR_HALF = 23;                // LDS words per lane
+constexpr int PR_LD = 2 * PR_HALF;         // 46 words per cell row
+constexpr int PR_CONV_H = IB_CONV / 2;     // 13 conv sums per lane
+constexpr int PR_POOL_H = S1_WSZ / 2;      // 8 pool products per lane
+constexpr int PR_D2_POS = PR_HALF + PR_CONV_H + PR_POOL_H;  // 44, lane 1
+constexpr int PR_CONV_OWNERS = 2 * C1_CH * IB_CONV;         // 312 threads
+constexpr int PR_POOL_T0 = 320;            // first pool owner (8-aligned)
+constexpr int PR_POOL_LANES = 8;
+constexpr int PR_LOSS_T = PR_THREADS - 1;  // wave 7: no cell work in phase 3
+static_assert(IB_CONV % 2 == 0 && S1_K % 2 == 0 && PR_HALF % 2 == 1 &&
+                  PR_CONV_H + PR_POOL_H + 1 <= PR_HALF &&
+                  PR_ACTIVE <= 448 && PR_CONV_OWNERS <= PR_POOL_T0 &&
+                  PR_POOL_T0 % PR_POOL_LANES == 0 &&
+                  PR_POOL_T0 + PR_POOL_LANES * (S1_WSZ + 1) <= PR_THREADS &&
+                  S1_PIX % 2 == 0 && S1_OUT % PR_POOL_LANES == 0 &&
+                  FC_OUT * 16 <= PR_THREADS,
+              "pair layout");
+
+// Value of the other lane of the pair (lane ^ 1): one DPP quad permute.
+__device__ __forceinline__ float pair_other(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(
+      0, __float_as_int(v), 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true));
+}
+
+template <typename act_t>
+__global__ __launch_bounds__(PR_THREADS) void k_fwdbwd_pair(
+    const act_t* __restrict__ x, const float* __restrict__ params,
+    act_t* __restrict__ a2g, float* __restrict__ yg, float* __restrict__ dzg,
+    const int* __restrict__ labels, float* __restrict__ loss_accum, int B,
+    int pool_mode, int loss_mode, float* __restrict__ gslab) {
+  __shared__ float a2s[S1_OUT];
+  __shared__ float ys[FC_OUT];
+  __shared__ float dzs[FC_OUT];
+  __shared__ float sq[FC_OUT];
+  __shared__ float rows[S1_OUT * PR_LD];
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const int tid = threadIdx.x;
+  PCNN_STAMP(ST_ENTRY);
+  const bool active = tid < PR_ACTIVE;
+  const int cell = active ? tid >> 1 : S1_OUT - 1;
+  const int h = tid & 1;
+  const int o = cell / S1_PIX;
+  const int pq = cell - o * S1_PIX;
+  const int pr = pq / S1_W;
+  const int pc = pq - pr * S1_W;
+
+  // ---- every load of the kernel, before the first FMA ----
+  float xw[6][8];  // rows 2h .. 2h+5 of the cell's 8x8 window
+  {
+    const act_t* xb = x + (size_t)b * IN_PIX +
+                      (pr * S1_K + 2 * h) * IN_W + pc * S1_K;
+#pragma unroll
+    for (int u = 0; u < 6; ++u)
+#pragma unroll
+      for (int v4 = 0; v4 < 2; ++v4)
+        ld4f(xb + u * IN_W + v4 * 4, &xw[u][v4 * 4]);
+  }
+  float wv[C1_K * C1_K];
+#pragma unroll
+  for (int q = 0; q < C1_K * C1_K; ++q)
+    wv[q] = params[OFF_C1W + o * C1_K * C1_K + q];
+  const float cb = params[OFF_C1B + o];
+  float sw[PR_POOL_H];  // pool weights of this lane's two rows
+#pragma unroll
+  for (int t = 0; t < PR_POOL_H; ++t)
+    sw[t] = params[OFF_S1W + h * PR_POOL_H + t];
+  const float sb = params[OFF_S1B];
+  // phase 2: lane l of class k2 takes a2[l + 16u]; phase 3: the cell's column
+  const int k2 = (tid >> 4) < FC_OUT ? (tid >> 4) : FC_OUT - 1;
+  const int l = tid & 15;
+  constexpr int FC_U = (FC_IN + 15) / 16;  // 14
+  float wrow[FC_U];
+#pragma unroll
+  for (int u = 0; u < FC_U; ++u) {
+    const int m = l + u * 16;
+    wrow[u] = params[OFF_FW + k2 * FC_IN + (m < FC_IN ? m : FC_IN - 1)];
+  }
+  const float fb = params[OFF_FB + k2];
+  float fcol[FC_OUT];
+#pragma unroll
+  for (int k = 0; k < FC_OUT; ++k)
+    fcol[k] = params[OFF_FW + k * FC_IN + cell];
+  const int lab = labels[b];
+  __builtin_amdgcn_sched_barrier(0);
+  PCNN_STAMP_DRAIN();
+  PCNN_STAMP(ST_LOADS);
+
+  // ---- phase 1: conv1 + sigmoid + pool + sigmoid ----
+  float av[2 * S1_K];  // this lane's 8 conv activations, kept live to bwd
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+#pragma unroll
+    for (int j = 0; j < S1_K; ++j) {
+      float acc = cb;
+#pragma unroll
+      for (int u = 0; u < C1_K; ++u)
+#pragma unroll
+        for (int v = 0; v < C1_K; ++v)
+          acc = __builtin_fmaf(wv[u * C1_K + v], xw[i + u][j + v], acc);
+      av[i * S1_K + j] = sigmoidf_dev(acc);
+    }
+  }
+  // pool preact in the cell kernel's order: lane 0's 8 terms from the bias
+  // (or the max identity), then lane 1's 8 on top of lane 0's running value
+  float p0 = pool_mode == 1 ? -1e30f : sb;
+#pragma unroll
+  for (int t = 0; t < 2 * S1_K; ++t) {
+    if (pool_mode == 1)
+      p0 = fmaxf(p0, av[t]);
+    else
+      p0 = __builtin_fmaf(sw[t], av[t], p0);
+  }
+  float p1 = pair_other(p0);  // meaningful in lane 1: lane 0's sum
+#pragma unroll
+  for (int t = 0; t < 2 * S1_K; ++t) {
+    if (pool_mode == 1)
+      p1 = fmaxf(p1, av[t]);
+    else
+      p1 = __builtin_fmaf(sw[t], av[t], p1);
+  }
+  const float p1o = pair_other(p1);
+  const float a2v = sigmoidf_dev(h ? p1 : p1o);
+  if (active && h == 0) {
+    a2s[cell] = a2v;
+    stf(a2g + (size_t)b * S1_OUT + cell, a2v);
+  }
+  // the hoisted values are consumed here, so their loads stay above
+#pragma unroll
+  for (int u = 0; u < FC_U; ++u) asm volatile("" : "+v"(wrow[u]));
+#pragma unroll
+  for (int k = 0; k < FC_OUT; ++k) asm volatile("" : "+v"(fcol[k]));
+  PCNN_STAMP(ST_CONV);
+  __syncthreads();
+  PCNN_STAMP(ST_BAR1);
+
+  // ---- phase 2: fc (216 -> 10) + sigmoid + residual, as the cell kernel ----
+  if (tid < FC_OUT * 16) {
+    const int k = tid >> 4;
+    float p = 0.f;
+#pragma unroll
+    for (int u = 0; u < FC_U; ++u) {
+      const int m = l + u * 16;
+      if (m < FC_IN) p = __builtin_fmaf(wrow[u], a2s[m], p);
+    }
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) p += __shfl_down(p, off, 16);
+    if (l == 0) {
+      const float z = p + fb;
+      if (loss_mode == 1) {
+        ys[k] = z;  // raw logit; softmax finished below
+      } else {
+        const float v = sigmoidf_dev(z);
+        ys[k] = v;
+        if (yg != nullptr) yg[(size_t)b * FC_OUT + k] = v;
+        const float d = (k == lab ? 1.0f : 0.0f) - v;
+        dzs[k] = d;
+        sq[k] = d * d;
+        dzg[(size_t)b * FC_OUT + k] = d;
+      }
+    }
+  }
+  PCNN_STAMP(ST_FC);
+  __syncthreads();
+  if (loss_mode == 1) {
+    if (tid == 0) {
+      float mx = ys[0];
+#pragma unroll
+      for (int k = 1; k < FC_OUT; ++k) mx = fmaxf(mx, ys[k]);
+      float sum = 0.f;
+      float e[FC_OUT];
+#pragma unroll
+      for (int k = 0; k < FC_OUT; ++k) {
+        e[k] = __expf(ys[k] - mx);
+        sum += e[k];
+      }
+#pragma unroll
+      for (int k = 0; k < FC_OUT; ++k) {
+        const float v = e[k] / sum;
+        ys[k] = v;
+        if (yg != nullptr) yg[(size_t)b * FC_OUT + k] = v;
+        const float d = (k == lab ? 1.0f : 0.0f) - v;
+        dzs[k] = d;
+        dzg[(size_t)b * FC_OUT + k] = d;
+      }
+      sq[0] = -__logf(fmaxf(ys[lab], 1e-30f));
+    }
+    __syncthreads();
+  }
+  PCNN_STAMP(ST_BAR2);
+
+  // ---- phase 3: fc bwd -> pool bwd -> weight-grad partials ----
+  if (tid < 448) {  // wave-uniform: waves 0-6 hold the 432 pair lanes
+    float da = 0.f;
+#pragma unroll
+    for (int k = 0; k < FC_OUT; ++k) da = __builtin_fmaf(fcol[k], dzs[k], da);
+    const float d2 = da * a2v * (1.0f - a2v);
+    // max pooling: d2 goes to the cell's first maximum; the pair settles
+    // which lane holds it (lane 0 wins ties, as the ascending scan does)
+    int best = -1;
+    if (pool_mode == 1) {
+      float bv = av[0];
+      int bi = 0;
+#pragma unroll
+      for (int t = 1; t < 2 * S1_K; ++t)
+        if (av[t] > bv) {
+          bv = av[t];
+          bi = t;
+        }
+      const float ov = pair_other(bv);
+      const bool mine = h ? (bv > ov) : !(ov > bv);
+      best = mine ? bi : -1;
+    }
+    float dz1v[2 * S1_K];
+#pragma unroll
+    for (int t = 0; t < 2 * S1_K; ++t) {
+      const float a = av[t];
+      const float dd = pool_mode == 1 ? (t == best ? d2 : 0.f) : d2 * sw[t];
+      dz1v[t] = dd * a * (1.0f - a);
+    }
+    PCNN_STAMP(ST_BWD);
+    // conv1 partial of this half cell: 8 dz1 x the 6x8 window (200 FMAs).
+    // dz1 and a1 enter rounded to the activation dtype, as in the cell
+    // kernel.
+    float cacc[C1_K * C1_K];
+#pragma unroll
+    for (int w2 = 0; w2 < C1_K * C1_K; ++w2) cacc[w2] = 0.f;
+    float csum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < S1_K; ++j) {
+        const float d = (float)(act_t)dz1v[i * S1_K + j];
+        csum += d;
+#pragma unroll
+        for (int u = 0; u < C1_K; ++u)
+#pragma unroll
+          for (int v = 0; v < C1_K; ++v)
+            cacc[u * C1_K + v] += d * xw[i + u][j + v];
+      }
+    // pair sum: a + b is the same number in both lanes
+#pragma unroll
+    for (int w2 = 0; w2 < C1_K * C1_K; ++w2) cacc[w2] += pair_other(cacc[w2]);
+    csum += pair_other(csum);
+    PCNN_STAMP(ST_WGRAD);
+    if (active) {
+      float* row = rows + tid * PR_HALF;
+#pragma unroll
+      for (int s = 0; s < PR_CONV_H; ++s) {
+        const float hi = PR_CONV_H + s < C1_K * C1_K ? cacc[PR_CONV_H + s]
+                                                     : csum;
+        row[s] = h ? hi : cacc[s];
+      }
+      if (pool_mode == 0) {
+#pragma unroll
+        for (int t = 0; t < PR_POOL_H; ++t)
+          row[PR_CONV_H + t] = d2 * (float)(act_t)av[t];
+        if (h) row[PR_CONV_H + PR_POOL_H] = d2;
+      }
+    }
+    PCNN_STAMP_LDS_DRAIN();
+    PCNN_STAMP(ST_LDS);
+  } else if (tid == PR_LOSS_T && loss_accum != nullptr) {
+    if (loss_mode == 1) {
+      unsafeAtomicAdd(loss_accum, sq[0]);
+    } else {
+      float ssum = 0.f;
+#pragma unroll
+      for (int k = 0; k < FC_OUT; ++k) ssum += sq[k];
+      unsafeAtomicAdd(loss_accum, sqrtf(ssum));
+    }
+  }
+  __syncthreads();
+  PCNN_STAMP(ST_BAR3);
+
+  // ---- owners: fixed-order sums over the 216 cell rows ----
+  float* out = gslab + (size_t)b * GSLAB_LD;
+  if (tid < PR_CONV_OWNERS) {
+    // two lanes per (channel, 5x5 weight | bias), 18 of the 36 cells each
+    const int own = tid >> 1;
+    const int o2 = own / IB_CONV;
+    const int w2 = own - o2 * IB_CONV;
+    const int pos = w2 < PR_CONV_H ? w2 : PR_HALF + w2 - PR_CONV_H;
+    const float* col = rows + (o2 * S1_PIX + h * (S1_PIX / 2)) * PR_LD + pos;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int c = 0; c < S1_PIX / 2; c += 3) {
+      s0 += col[(c + 0) * PR_LD];
+      s1 += col[(c + 1) * PR_LD];
+      s2 += col[(c + 2) * PR_LD];
+    }
+    float s = (s0 + s1) + s2;
+    s += pair_other(s);
+    PCNN_STAMP(ST_OWNER);
+    if (h == 0)
+      out[w2 < C1_K * C1_K ? OFF_C1W + o2 * C1_K * C1_K + w2 : OFF_C1B + o2] =
+          s * (1.0f / (float)C1_PIX);
+  } else if (tid >= PR_POOL_T0 &&
+             tid < PR_POOL_T0 + PR_POOL_LANES * (S1_WSZ + 1)) {
+    // eight adjacent lanes per pool output, 27 cell rows each
+    const int q = tid - PR_POOL_T0;
+    const int w2 = q >> 3;
+    const int part = q & (PR_POOL_LANES - 1);
+    constexpr int RP = S1_OUT / PR_POOL_LANES;  // 27
+    float s = 0.f;
+    if (pool_mode == 0) {
+      const int pos = w2 < S1_WSZ
+                          ? (w2 / PR_POOL_H) * PR_HALF + PR_CONV_H +
+                                w2 % PR_POOL_H
+                          : PR_D2_POS;
+      const float* col = rows + part * RP * PR_LD + pos;
+      float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int c = 0; c < RP; c += 3) {
+        s0 += col[(c + 0) * PR_LD];
+        s1 += col[(c + 1) * PR_LD];
+        s2 += col[(c + 2) * PR_LD];
+      }
+      s = (s0 + s1) + s2;
+    }
+    s += __shfl_xor(s, 1, PR_POOL_LANES);
+    s += __shfl_xor(s, 2, PR_POOL_LANES);
+    s += __shfl_xor(s, 4, PR_POOL_LANES);
+    PCNN_STAMP(ST_OWNER);
+    if (part == 0)
+      out[OFF_S1W + w2] = w2 < S1_WSZ ? s : s * (1.0f / (float)S1_OUT);
+  }
+  PCNN_STAMP_DRAIN();
+  PCNN_STAMP(ST_END);
 }
 
 // ---------------------------------------------------------------------------
@@ -988,6 +1429,9 @@ constexpr int RU_BLOCKS =
 // Largest batch the step launcher gives to this pair of kernels (measured
 // crossover: pcnn_launch_step_inblock).
 constexpr int INBLOCK_MAX_B = 256;
+// Kernel 1 of the in-block step when the caller does not choose: 0 = cell
+// (k_fwdbwd<.., INBLOCK>), 1 = pair (k_fwdbwd_pair).
+constexpr int INBLOCK_DEFAULT_VARIANT = 1;
 
 // MOM selects the apply at the end and nothing else: the plain kernel is the
 // MOM=false instantiation with vel and o unused, the momentum kernel has the
@@ -1277,18 +1721,42 @@ int pcnn_launch_wgrad_update(const void* x, const void* a1, const void* a2,
                           chunk_imgs, roles, params, step, ticket, stream);
 }
 
-// First kernel of the in-block weight-grad step: k_fwdbwd<.., INBLOCK> in
-// train mode.  Writes a2, y, dz, the loss sum and rows [0, B) of gslab
-// ([>= B][GSLAB_LD] fp32); a1, dz1 and dz2 are not produced.
-int pcnn_launch_fwdbwd_inblock(const void* x, const float* params, void* a2,
-                               float* y, float* dz, const int* labels,
-                               float* loss_accum, float* gslab, int B,
-                               int act_is_bf16, int pool_mode, int loss_mode,
-                               void* stream) {
-  if (gslab == nullptr || dz == nullptr || B < 1)
+// Which kernel forms the slab: 0 = cell (k_fwdbwd<.., INBLOCK>, one lane per
+// pool cell, 256 threads), 1 = pair (k_fwdbwd_pair, two lanes per cell, 512
+// threads), -1 = the default below.
+int pcnn_inblock_default_variant() { return INBLOCK_DEFAULT_VARIANT; }
+
+// First kernel of the in-block weight-grad step in train mode.  Writes a2,
+// y, dz, the loss sum and rows [0, B) of gslab ([>= B][GSLAB_LD] fp32); a1,
+// dz1 and dz2 are not produced.
+int pcnn_launch_fwdbwd_inblock_v(const void* x, const float* params, void* a2,
+                                 float* y, float* dz, const int* labels,
+                                 float* loss_accum, float* gslab, int B,
+                                 int act_is_bf16, int pool_mode,
+                                 int loss_mode, int variant, void* stream) {
+  if (gslab == nullptr || dz == nullptr || B < 1 || variant < -1 ||
+      variant > 1)
     return (int)hipErrorInvalidValue;
-  dim3 grid(B), block(256);
+  if (variant < 0) variant = INBLOCK_DEFAULT_VARIANT;
   hipStream_t s = (hipStream_t)stream;
+  if (variant == 1) {
+    dim3 grid(B), block(PR_THREADS);
+    if (act_is_bf16 == 1) {
+      hipLaunchKernelGGL((k_fwdbwd_pair<bf16>), grid, block, 0, s,
+                         (const bf16*)x, params, (bf16*)a2, y, dz, labels,
+                         loss_accum, B, pool_mode, loss_mode, gslab);
+    } else if (act_is_bf16 == 2) {
+      hipLaunchKernelGGL((k_fwdbwd_pair<fp16>), grid, block, 0, s,
+                         (const fp16*)x, params, (fp16*)a2, y, dz, labels,
+                         loss_accum, B, pool_mode, loss_mode, gslab);
+    } else {
+      hipLaunchKernelGGL((k_fwdbwd_pair<float>), grid, block, 0, s,
+                         (const float*)x, params, (float*)a2, y, dz, labels,
+                         loss_accum, B, pool_mode, loss_mode, gslab);
+    }
+    return (int)hipGetLastError();
+  }
+  dim3 grid(B), block(256);
   if (act_is_bf16 == 1) {
     hipLaunchKernelGGL((k_fwdbwd<bf16, MODE_TRAIN, true>), grid, block, 0, s,
                        (const bf16*)x, params, (bf16*)nullptr, (bf16*)a2, y,
@@ -1309,6 +1777,16 @@ int pcnn_launch_fwdbwd_inblock(const void* x, const float* params, void* a2,
                        gslab, 0);
   }
   return (int)hipGetLastError();
+}
+
+int pcnn_launch_fwdbwd_inblock(const void* x, const float* params, void* a2,
+                               float* y, float* dz, const int* labels,
+                               float* loss_accum, float* gslab, int B,
+                               int act_is_bf16, int pool_mode, int loss_mode,
+                               void* stream) {
+  return pcnn_launch_fwdbwd_inblock_v(x, params, a2, y, dz, labels,
+                                      loss_accum, gslab, B, act_is_bf16,
+                                      pool_mode, loss_mode, -1, stream);
 }
 
 // Second kernel of the in-block weight-grad step (k_reduce_update).
@@ -1340,13 +1818,13 @@ int pcnn_inblock_max_batch() { return INBLOCK_MAX_B; }
 // k_fwdbwd<INBLOCK> -> k_reduce_update.  `grads` and `ticket` are only
 // touched by the large-batch fallback and read all-zero / 0 afterwards
 // either way.
-int pcnn_launch_step_inblock(const void* x, float* params, void* a1, void* a2,
-                             float* y, float* dz, float* dz2, void* dz1,
-                             const int* labels, float* loss_accum,
-                             float* grads, int* ticket, float* gslab,
-                             float step, int B, int act_is_bf16,
-                             int pool_mode, int loss_mode, int chunk_imgs,
-                             void* stream) {
+int pcnn_launch_step_inblock_v(const void* x, float* params, void* a1,
+                               void* a2, float* y, float* dz, float* dz2,
+                               void* dz1, const int* labels,
+                               float* loss_accum, float* grads, int* ticket,
+                               float* gslab, float step, int B,
+                               int act_is_bf16, int pool_mode, int loss_mode,
+                               int chunk_imgs, int variant, void* stream) {
   // k_reduce_update walks the batch with 4 lanes per parameter, so its cost
   // grows linearly with B while k_wgrad_update spreads a larger batch over
   // more blocks.  Measured (MI355X, bf16, us/step, in-block vs
@@ -1369,12 +1847,26 @@ int pcnn_launch_step_inblock(const void* x, float* params, void* a1, void* a2,
                                     step, ticket, B, act_is_bf16, chunk_imgs,
                                     pool_mode == 1 ? 5 : 7, stream);
   }
-  int err = pcnn_launch_fwdbwd_inblock(x, params, a2, y, dz, labels,
-                                       loss_accum, gslab, B, act_is_bf16,
-                                       pool_mode, loss_mode, stream);
+  int err = pcnn_launch_fwdbwd_inblock_v(x, params, a2, y, dz, labels,
+                                         loss_accum, gslab, B, act_is_bf16,
+                                         pool_mode, loss_mode, variant,
+                                         stream);
   if (err != 0) return err;
   return pcnn_launch_reduce_update(gslab, a2, dz, params, step, B,
                                    act_is_bf16, stream);
+}
+
+int pcnn_launch_step_inblock(const void* x, float* params, void* a1, void* a2,
+                             float* y, float* dz, float* dz2, void* dz1,
+                             const int* labels, float* loss_accum,
+                             float* grads, int* ticket, float* gslab,
+                             float step, int B, int act_is_bf16,
+                             int pool_mode, int loss_mode, int chunk_imgs,
+                             void* stream) {
+  return pcnn_launch_step_inblock_v(x, params, a1, a2, y, dz, dz2, dz1,
+                                    labels, loss_accum, grads, ticket, gslab,
+                                    step, B, act_is_bf16, pool_mode,
+                                    loss_mode, chunk_imgs, -1, stream);
 }
 
 int pcnn_launch_wgrad(const void* x, const void* a1, const void* a2,
@@ -1458,15 +1950,15 @@ int pcnn_launch_reduce_update_mom(const float* gslab, const void* a2,
 
 // pcnn_launch_step_inblock with the momentum update; the B > INBLOCK_MAX_B
 // hand-off goes to k_wgrad_update_mom with the same optimizer arguments.
-int pcnn_launch_step_inblock_mom(const void* x, float* params, float* vel,
-                                 void* a1, void* a2, float* y, float* dz,
-                                 float* dz2, void* dz1, const int* labels,
-                                 float* loss_accum, float* grads, int* ticket,
-                                 float* gslab, float scale, float dt,
-                                 float mu, float wd, int nesterov, int B,
-                                 int act_is_bf16, int pool_mode,
-                                 int loss_mode, int chunk_imgs,
-                                 void* stream) {
+int pcnn_launch_step_inblock_mom_v(const void* x, float* params, float* vel,
+                                   void* a1, void* a2, float* y, float* dz,
+                                   float* dz2, void* dz1, const int* labels,
+                                   float* loss_accum, float* grads,
+                                   int* ticket, float* gslab, float scale,
+                                   float dt, float mu, float wd, int nesterov,
+                                   int B, int act_is_bf16, int pool_mode,
+                                   int loss_mode, int chunk_imgs, int variant,
+                                   void* stream) {
   if (B > INBLOCK_MAX_B) {
     int err = pcnn_launch_fwdbwd_ex2(x, params, a1, a2, y, dz, dz2, dz1,
                                      labels, loss_accum, nullptr, B,
@@ -1479,14 +1971,43 @@ int pcnn_launch_step_inblock_mom(const void* x, float* params, float* vel,
                                         chunk_imgs, pool_mode == 1 ? 5 : 7,
                                         stream);
   }
-  int err = pcnn_launch_fwdbwd_inblock(x, params, a2, y, dz, labels,
-                                       loss_accum, gslab, B, act_is_bf16,
-                                       pool_mode, loss_mode, stream);
+  int err = pcnn_launch_fwdbwd_inblock_v(x, params, a2, y, dz, labels,
+                                         loss_accum, gslab, B, act_is_bf16,
+                                         pool_mode, loss_mode, variant,
+                                         stream);
   if (err != 0) return err;
   return pcnn_launch_reduce_update_mom(gslab, a2, dz, params, vel, scale, dt,
                                        mu, wd, nesterov, B, act_is_bf16,
                                        stream);
 }
+
+int pcnn_launch_step_inblock_mom(const void* x, float* params, float* vel,
+                                 void* a1, void* a2, float* y, float* dz,
+                                 float* dz2, void* dz1, const int* labels,
+                                 float* loss_accum, float* grads, int* ticket,
+                                 float* gslab, float scale, float dt,
+                                 float mu, float wd, int nesterov, int B,
+                                 int act_is_bf16, int pool_mode,
+                                 int loss_mode, int chunk_imgs,
+                                 void* stream) {
+  return pcnn_launch_step_inblock_mom_v(x, params, vel, a1, a2, y, dz, dz2,
+                                        dz1, labels, loss_accum, grads,
+                                        ticket, gslab, scale, dt, mu, wd,
+                                        nesterov, B, act_is_bf16, pool_mode,
+                                        loss_mode, chunk_imgs, -1, stream);
+}
+
+#ifdef PCNN_LENET_STAMPS
+// Diagnostic build only: side buffer of the phase stamps,
+// [blocks][512][16] 64-bit words.
+int pcnn_stamp_set_buffer(void* buf, int blocks) {
+  unsigned long long* p = (unsigned long long*)buf;
+  hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(pcnn::g_stamps), &p, sizeof(p));
+  if (e != hipSuccess) return (int)e;
+  return (int)hipMemcpyToSymbol(HIP_SYMBOL(pcnn::g_stamp_blocks), &blocks,
+                                sizeof(blocks));
+}
+#endif
 
 const char* pcnn_hip_error_string(int err) {
   return hipGetErrorString((hipError_t)err);

@@ -125,6 +125,17 @@ class Trainer:
             raise ValueError(
                 f"PCNN_LENET_WGRAD must be inblock or grid, got {wg!r}")
         self._wgrad_inblock = wg == "inblock"
+        # which kernel forms the slab in the in-block step, read once here:
+        # PCNN_LENET_FWDBWD=pair is k_fwdbwd_pair (two lanes per pool cell,
+        # 512-thread blocks), cell is k_fwdbwd<INBLOCK> (one lane per cell,
+        # 256 threads); unset takes the extension's default
+        # (_C.INBLOCK_DEFAULT_VARIANT).  No effect where the in-block step
+        # does not run: PCNN_LENET_STEP=3, PCNN_LENET_WGRAD=grid, B > 256.
+        fb = os.environ.get("PCNN_LENET_FWDBWD")
+        if fb not in (None, "pair", "cell"):
+            raise ValueError(
+                f"PCNN_LENET_FWDBWD must be pair or cell, got {fb!r}")
+        self._inblock_variant = {None: -1, "cell": 0, "pair": 1}[fb]
 
     def _fused_step_mode(self) -> int:
         """2 when the update may run inside the wgrad launch: nothing may
@@ -149,14 +160,15 @@ class Trainer:
                 x, m.params, self.vel, w.a1, w.a2, w.y, w.dz, w.dz2, w.dz1,
                 labels, w.loss_accum, m.grads, w.ticket, w.gslab,
                 *self._opt_args(B), B, self.cfg.wgrad_chunk, stream,
-                self._pool_mode, self._loss_mode)
+                self._pool_mode, self._loss_mode, self._inblock_variant)
             return
         self._C.hip_step_inblock(x, m.params, w.a1, w.a2, w.y, w.dz, w.dz2,
                                  w.dz1, labels, w.loss_accum, m.grads,
                                  w.ticket, w.gslab,
                                  self.cfg.dt * self._update_scale(B), B,
                                  self.cfg.wgrad_chunk, stream,
-                                 self._pool_mode, self._loss_mode)
+                                 self._pool_mode, self._loss_mode,
+                                 self._inblock_variant)
 
     # ------------------------------------------------------------------ util
     def _update_scale(self, local_batch: int) -> float:
@@ -439,7 +451,7 @@ class Trainer:
                 native.current_stream_handle(), self._pool_mode,
                 self._loss_mode, self._fuse,
                 4 if self._use_inblock() else self._fused_step_mode(),
-                w.ticket, w.gslab, **opt)
+                w.ticket, w.gslab, variant=self._inblock_variant, **opt)
             self._samples_seen += B * steps
             self.global_step += steps
         else:
