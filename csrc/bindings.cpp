@@ -1,14 +1,16 @@
 // pybind11 bindings for parallel_cnn_amd._C
 //
 // CPU ops take at::Tensor directly.  GPU launchers live in
-// csrc/hip/lenet_kernels.hip (compiled by hipcc for gfx950, linked in as
-// objects); this translation unit deliberately includes no HIP headers —
+// csrc/hip/*.hip (compiled by hipcc for gfx950, linked in as objects) and
+// are declared in pcnn_launch.h, the only place their prototypes are
+// written; this translation unit deliberately includes no HIP headers —
 // streams cross the boundary as opaque pointers obtained from
 // torch.cuda.current_stream().cuda_stream on the Python side.
 
 #include <torch/extension.h>
 
 #include "lenet_dims.h"
+#include "pcnn_launch.h"
 
 namespace pcnn {
 void cpu_forward(at::Tensor x, at::Tensor params, at::Tensor a1, at::Tensor a2,
@@ -22,194 +24,6 @@ void cpu_update_momentum(at::Tensor params, at::Tensor grads, at::Tensor vel,
                          double dt, double scale, double mu, double wd,
                          bool nesterov);
 }  // namespace pcnn
-
-extern "C" {
-int pcnn_launch_fwdbwd(const void* x, const float* params, void* a1, void* a2,
-                       float* y, float* dz, float* dz2, void* dz1,
-                       const int* labels, float* loss_accum, int* correct,
-                       int B, int act_is_bf16, int mode, void* stream);
-int pcnn_launch_fwdbwd_ex(const void* x, const float* params, void* a1,
-                          void* a2, float* y, float* dz, float* dz2,
-                          void* dz1, const int* labels, float* loss_accum,
-                          int* correct, int B, int act_is_bf16, int mode,
-                          int pool_mode, int loss_mode, void* stream);
-int pcnn_launch_fwdbwd_ex2(const void* x, const float* params, void* a1,
-                           void* a2, float* y, float* dz, float* dz2,
-                           void* dz1, const int* labels, float* loss_accum,
-                           int* correct, int B, int act_is_bf16, int mode,
-                           int pool_mode, int loss_mode, float* grads,
-                           int wgrad_fuse, void* stream);
-int pcnn_launch_wgrad(const void* x, const void* a1, const void* a2,
-                      const float* dz, const float* dz2, const void* dz1,
-                      float* grads, int B, int act_is_bf16, int chunk_imgs,
-                      void* stream);
-int pcnn_launch_wgrad_ex(const void* x, const void* a1, const void* a2,
-                         const float* dz, const float* dz2, const void* dz1,
-                         float* grads, int B, int act_is_bf16, int chunk_imgs,
-                         int roles, void* stream);
-int pcnn_launch_update(float* params, float* grads, float step, void* stream);
-int pcnn_launch_wgrad_update(const void* x, const void* a1, const void* a2,
-                             const float* dz, const float* dz2,
-                             const void* dz1, float* grads, float* params,
-                             float step, int* ticket, int B, int act_is_bf16,
-                             int chunk_imgs, int roles, void* stream);
-int pcnn_launch_fwdbwd_inblock(const void* x, const float* params, void* a2,
-                               float* y, float* dz, const int* labels,
-                               float* loss_accum, float* gslab, int B,
-                               int act_is_bf16, int pool_mode, int loss_mode,
-                               void* stream);
-int pcnn_launch_reduce_update(const float* gslab, const void* a2,
-                              const float* dz, float* params, float step,
-                              int B, int act_is_bf16, void* stream);
-int pcnn_inblock_max_batch();
-// _v launchers: variant 0 = cell kernel, 1 = pair kernel, -1 = default
-int pcnn_inblock_default_variant();
-int pcnn_launch_fwdbwd_inblock_v(const void* x, const float* params, void* a2,
-                                 float* y, float* dz, const int* labels,
-                                 float* loss_accum, float* gslab, int B,
-                                 int act_is_bf16, int pool_mode,
-                                 int loss_mode, int variant, void* stream);
-int pcnn_launch_step_inblock_v(const void* x, float* params, void* a1,
-                               void* a2, float* y, float* dz, float* dz2,
-                               void* dz1, const int* labels,
-                               float* loss_accum, float* grads, int* ticket,
-                               float* gslab, float step, int B,
-                               int act_is_bf16, int pool_mode, int loss_mode,
-                               int chunk_imgs, int variant, void* stream);
-int pcnn_launch_step_inblock_mom_v(const void* x, float* params, float* vel,
-                                   void* a1, void* a2, float* y, float* dz,
-                                   float* dz2, void* dz1, const int* labels,
-                                   float* loss_accum, float* grads,
-                                   int* ticket, float* gslab, float scale,
-                                   float dt, float mu, float wd, int nesterov,
-                                   int B, int act_is_bf16, int pool_mode,
-                                   int loss_mode, int chunk_imgs, int variant,
-                                   void* stream);
-int pcnn_launch_step_inblock(const void* x, float* params, void* a1, void* a2,
-                             float* y, float* dz, float* dz2, void* dz1,
-                             const int* labels, float* loss_accum,
-                             float* grads, int* ticket, float* gslab,
-                             float step, int B, int act_is_bf16,
-                             int pool_mode, int loss_mode, int chunk_imgs,
-                             void* stream);
-// momentum variants: scale and dt apart, vel = fp32 velocity bucket
-int pcnn_launch_update_mom(float* params, float* grads, float* vel,
-                           float scale, float dt, float mu, float wd,
-                           int nesterov, void* stream);
-int pcnn_launch_wgrad_update_mom(const void* x, const void* a1,
-                                 const void* a2, const float* dz,
-                                 const float* dz2, const void* dz1,
-                                 float* grads, float* params, float* vel,
-                                 float scale, float dt, float mu, float wd,
-                                 int nesterov, int* ticket, int B,
-                                 int act_is_bf16, int chunk_imgs, int roles,
-                                 void* stream);
-int pcnn_launch_reduce_update_mom(const float* gslab, const void* a2,
-                                  const float* dz, float* params, float* vel,
-                                  float scale, float dt, float mu, float wd,
-                                  int nesterov, int B, int act_is_bf16,
-                                  void* stream);
-int pcnn_launch_step_inblock_mom(const void* x, float* params, float* vel,
-                                 void* a1, void* a2, float* y, float* dz,
-                                 float* dz2, void* dz1, const int* labels,
-                                 float* loss_accum, float* grads, int* ticket,
-                                 float* gslab, float scale, float dt,
-                                 float mu, float wd, int nesterov, int B,
-                                 int act_is_bf16, int pool_mode,
-                                 int loss_mode, int chunk_imgs,
-                                 void* stream);
-int pcnn_deep_update_cast_mom(float* params, float* grads, float* vel,
-                              long long n, float scale, float dt, float mu,
-                              float wd, int nesterov, void* wbuf,
-                              int n_stages, const int* R, const int* C,
-                              const int* K, const int* Cin,
-                              const long long* w_off, const long long* bf_off,
-                              const long long* bfT_off,
-                              const long long* rot_off,
-                              const long long* p8_off, void* stream);
-int pcnn_deep_update_mom(float* params, float* grads, float* vel, long long n,
-                         float scale, float dt, float mu, float wd,
-                         int nesterov, void* stream);
-const char* pcnn_hip_error_string(int err);
-// deep (general conv) kernels — csrc/hip/conv_kernels.hip
-int pcnn_deep_im2col(const void* x, void* cols, int B, int H, int W, int Cin,
-                     int K, int P, int KcP, int actf, void* stream);
-int pcnn_deep_gemm(const void* A, const float* Bsrc, const float* bias,
-                   void* C, long long M, int K, int N, int ldA, int ldC,
-                   int b_kxn, int epilogue, int actf, void* stream);
-int pcnn_deep_gemm_ex4(const void* A, const float* Bsrc, const void* Bpre,
-                       const float* bias, void* C, long long M, int K, int N,
-                       int ldA, int ldC, int b_kxn, int epilogue,
-                       const void* imx, int XH, int XW, int XC, int XK,
-                       int XP, const void* epi, const float* pw, void* pout,
-                       int PK, float* c32, long long c32_cap, int actf,
-                       void* stream);
-int pcnn_deep_wgrad_gemm_ex2(const void* cols, const void* dpre, float* dW,
-                             float* part, long long M, int KcP, int N,
-                             int MS, const void* imx, int XH, int XW, int XC,
-                             int XK, int XP, float* db, int actf,
-                             void* stream);
-int pcnn_deep_cast_wt(const float* W, void* out, void* outT, int R, int C,
-                      void* stream);
-int pcnn_deep_cast_all(const float* params, void* wbuf, int n_stages,
-                       const int* R, const int* C, const int* K,
-                       const int* Cin, const long long* w_off,
-                       const long long* bf_off, const long long* bfT_off,
-                       const long long* rot_off, const long long* p8_off,
-                       void* stream);
-int pcnn_deep_wgrad_multi(int n_stages, const void* const* a,
-                          const void* const* dpre, float* const* dW,
-                          float* const* db, const long long* M,
-                          const int* KcP, const int* N, const int* MS,
-                          const int* implicit, const int* XH, const int* XW,
-                          const int* XC, const int* XK, const int* XP,
-                          int actf, void* stream);
-int pcnn_deep_update_cast(float* params, float* grads, long long n,
-                          float step, void* wbuf, int n_stages, const int* R,
-                          const int* C, const int* K, const int* Cin,
-                          const long long* w_off, const long long* bf_off,
-                          const long long* bfT_off, const long long* rot_off,
-                          const long long* p8_off, void* stream);
-int pcnn_deep_pad_channels(const void* x, void* x8, long long npix, int Cin,
-                           int actf, void* stream);
-int pcnn_deep_remap_dw8(float* dW8, float* dW, int KK, int Cin, int Cout,
-                        void* stream);
-int pcnn_deep_wgrad_gemm(const void* cols, const void* dpre, float* dW,
-                         float* part, long long M, int KcP, int N, int MS,
-                         int actf, void* stream);
-int pcnn_deep_colsum(const void* dpre, float* part, float* db, long long M,
-                     int N,
-                     int slices, int actf, void* stream);
-int pcnn_deep_col2im_sigbwd(const void* dcols, const void* pout, void* out,
-                            int B, int H, int W, int Cin, int K, int P,
-                            int KcP, int actf, void* stream);
-int pcnn_deep_pool_fwd(const void* a, const float* pw, void* pout, int B,
-                       int H, int W, int C, int K, int actf, void* stream);
-int pcnn_deep_pool_bwd(const void* dppre, const void* a, const float* pw,
-                       void* dapre, int B, int H, int W, int C, int K,
-                       int actf, void* stream);
-int pcnn_deep_pool_wgrad(const void* dppre, const void* a, float* dpw, int B,
-                         int H, int W, int C, int K, int G, int actf,
-                         void* stream);
-int pcnn_deep_pool_wbwd(const void* dppre, const void* a, const float* pw,
-                        void* dapre, float* dpw, int B, int H, int W, int C,
-                        int K, int G, int actf, void* stream);
-int pcnn_deep_fc_fwd2(const void* flat, const float* fw, const float* fb,
-                      const int* labels, float* yg, float* dzg,
-                      float* loss_accum, int* correct_accum, int B, int FCIN,
-                      int NCLS, int mode, void* dflat, int actf,
-                      void* stream);
-int pcnn_deep_fc_bwd(const float* dzg, const void* flat, const float* fw,
-                     void* dflat, int B, int FCIN, int NCLS, int actf,
-                     void* stream);
-int pcnn_deep_fc_wgrad(const float* dzg, const void* flat, float* gfw,
-                       float* gfb, int B, int FCIN, int NCLS, int FS,
-                       int actf, void* stream);
-int pcnn_deep_update(float* params, float* grads, long long n, float step,
-                     void* stream);
-int pcnn_deep_mfma_selftest(const float* A, const float* Bm, float* D,
-                            void* stream);
-}
 
 namespace {
 
@@ -238,7 +52,7 @@ void hip_fwdbwd(at::Tensor x, at::Tensor params, at::Tensor a1, at::Tensor a2,
   TORCH_CHECK(!dz1.numel() || dz1.scalar_type() == x.scalar_type(),
               "dz1 must match the activation dtype");
   int f = act_flag(x);
-  check_hip(pcnn_launch_fwdbwd_ex2(
+  check_hip(pcnn_launch_fwdbwd(
                 x.data_ptr(), params.data_ptr<float>(), a1.data_ptr(),
                 a2.data_ptr(), y.numel() ? y.data_ptr<float>() : nullptr,
                 dz.numel() ? dz.data_ptr<float>() : nullptr,
@@ -253,39 +67,29 @@ void hip_fwdbwd(at::Tensor x, at::Tensor params, at::Tensor a1, at::Tensor a2,
             "fwdbwd");
 }
 
-void hip_wgrad(at::Tensor x, at::Tensor a1, at::Tensor a2, at::Tensor dz,
-               at::Tensor dz2, at::Tensor dz1, at::Tensor grads, int64_t B,
-               int64_t chunk_imgs, int64_t stream) {
-  int f = act_flag(x);
-  TORCH_CHECK(dz1.scalar_type() == x.scalar_type(),
-              "dz1 must match the activation dtype");
-  check_hip(pcnn_launch_wgrad(x.data_ptr(), a1.data_ptr(), a2.data_ptr(),
-                              dz.data_ptr<float>(), dz2.data_ptr<float>(),
-                              dz1.data_ptr(), grads.data_ptr<float>(),
-                              (int)B, f, (int)chunk_imgs, (void*)stream),
-            "wgrad");
-}
-
 // roles bitmask (1=conv1, 2=pool, 4=fc) — ablation/diagnostics only.
 void hip_wgrad_roles(at::Tensor x, at::Tensor a1, at::Tensor a2,
                      at::Tensor dz, at::Tensor dz2, at::Tensor dz1,
                      at::Tensor grads, int64_t B, int64_t chunk_imgs,
                      int64_t roles, int64_t stream) {
   int f = act_flag(x);
-  check_hip(pcnn_launch_wgrad_ex(x.data_ptr(), a1.data_ptr(), a2.data_ptr(),
-                                 dz.data_ptr<float>(), dz2.data_ptr<float>(),
-                                 dz1.data_ptr(), grads.data_ptr<float>(),
-                                 (int)B, f, (int)chunk_imgs, (int)roles,
-                                 (void*)stream),
+  check_hip(pcnn_launch_wgrad(x.data_ptr(), a1.data_ptr(), a2.data_ptr(),
+                              dz.data_ptr<float>(), dz2.data_ptr<float>(),
+                              dz1.data_ptr(), grads.data_ptr<float>(), (int)B,
+                              f, (int)chunk_imgs, (int)roles, (void*)stream),
             "wgrad_roles");
 }
 
-void hip_update(at::Tensor params, at::Tensor grads, double step,
-                int64_t stream) {
-  check_hip(pcnn_launch_update(params.data_ptr<float>(),
-                               grads.data_ptr<float>(), (float)step,
-                               (void*)stream),
-            "update");
+void hip_wgrad(at::Tensor x, at::Tensor a1, at::Tensor a2, at::Tensor dz,
+               at::Tensor dz2, at::Tensor dz1, at::Tensor grads, int64_t B,
+               int64_t chunk_imgs, int64_t stream) {
+  TORCH_CHECK(dz1.scalar_type() == x.scalar_type(),
+              "dz1 must match the activation dtype");
+  check_hip(pcnn_launch_wgrad(x.data_ptr(), a1.data_ptr(), a2.data_ptr(),
+                              dz.data_ptr<float>(), dz2.data_ptr<float>(),
+                              dz1.data_ptr(), grads.data_ptr<float>(), (int)B,
+                              act_flag(x), (int)chunk_imgs, 7, (void*)stream),
+            "wgrad");
 }
 
 int* ticket_ptr(const at::Tensor& ticket) {
@@ -295,30 +99,7 @@ int* ticket_ptr(const at::Tensor& ticket) {
   return ticket.data_ptr<int>();
 }
 
-// Weight gradients with the SGD update as the tail of the same launch:
-// the last block to arrive on `ticket` applies p += step*g and zeroes g.
-void hip_wgrad_update(at::Tensor x, at::Tensor a1, at::Tensor a2,
-                      at::Tensor dz, at::Tensor dz2, at::Tensor dz1,
-                      at::Tensor grads, at::Tensor params, double step,
-                      at::Tensor ticket, int64_t B, int64_t chunk_imgs,
-                      int64_t roles, int64_t stream) {
-  int f = act_flag(x);
-  TORCH_CHECK(dz1.scalar_type() == x.scalar_type(),
-              "dz1 must match the activation dtype");
-  TORCH_CHECK(params.is_cuda() && grads.is_cuda() &&
-                  params.numel() == pcnn::N_PARAMS &&
-                  grads.numel() == pcnn::N_PARAMS,
-              "params/grads must be the flat device buckets");
-  check_hip(pcnn_launch_wgrad_update(
-                x.data_ptr(), a1.data_ptr(), a2.data_ptr(),
-                dz.data_ptr<float>(), dz2.data_ptr<float>(), dz1.data_ptr(),
-                grads.data_ptr<float>(), params.data_ptr<float>(),
-                (float)step, ticket_ptr(ticket), (int)B, f, (int)chunk_imgs,
-                (int)roles, (void*)stream),
-            "wgrad_update");
-}
-
-// Velocity bucket of the momentum update variants.
+// Velocity bucket of the momentum update.
 float* vel_ptr(const at::Tensor& vel, const at::Tensor& params) {
   TORCH_CHECK(vel.is_cuda() && vel.scalar_type() == at::kFloat &&
                   vel.is_contiguous() && vel.numel() == params.numel(),
@@ -327,20 +108,76 @@ float* vel_ptr(const at::Tensor& vel, const at::Tensor& params) {
   return vel.data_ptr<float>();
 }
 
-// hip_update with momentum / Nesterov / weight decay (k_update_mom).
-void hip_update_momentum(at::Tensor params, at::Tensor grads, at::Tensor vel,
-                         double dt, double scale, double mu, double wd,
-                         bool nesterov, int64_t stream) {
+// The optimizer of a launch (pcnn_opt, pcnn_launch.h): the plain bindings
+// pass the pre-multiplied step and no velocity, which selects the plain
+// kernels; the _momentum bindings pass dt and scale apart and the velocity
+// bucket.
+pcnn_opt plain_opt(double step) {
+  return pcnn_opt{(float)step, 0.f, 0.f, 0.f, 0.f, 0, nullptr};
+}
+
+pcnn_opt momentum_opt(const at::Tensor& vel, const at::Tensor& params,
+                      double dt, double scale, double mu, double wd,
+                      bool nesterov) {
+  return pcnn_opt{0.f,       (float)scale,     (float)dt,           (float)mu,
+                  (float)wd, nesterov ? 1 : 0, vel_ptr(vel, params)};
+}
+
+void check_flat_buckets(const at::Tensor& params, const at::Tensor& grads) {
   TORCH_CHECK(params.is_cuda() && grads.is_cuda() &&
                   params.numel() == pcnn::N_PARAMS &&
                   grads.numel() == pcnn::N_PARAMS,
               "params/grads must be the flat device buckets");
-  check_hip(pcnn_launch_update_mom(params.data_ptr<float>(),
-                                   grads.data_ptr<float>(),
-                                   vel_ptr(vel, params), (float)scale,
-                                   (float)dt, (float)mu, (float)wd,
-                                   nesterov ? 1 : 0, (void*)stream),
+}
+
+void hip_update(at::Tensor params, at::Tensor grads, double step,
+                int64_t stream) {
+  const pcnn_opt opt = plain_opt(step);
+  check_hip(pcnn_launch_update(params.data_ptr<float>(),
+                               grads.data_ptr<float>(), &opt, (void*)stream),
+            "update");
+}
+
+// hip_update with momentum / Nesterov / weight decay (k_update_mom).
+void hip_update_momentum(at::Tensor params, at::Tensor grads, at::Tensor vel,
+                         double dt, double scale, double mu, double wd,
+                         bool nesterov, int64_t stream) {
+  check_flat_buckets(params, grads);
+  const pcnn_opt opt = momentum_opt(vel, params, dt, scale, mu, wd, nesterov);
+  check_hip(pcnn_launch_update(params.data_ptr<float>(),
+                               grads.data_ptr<float>(), &opt, (void*)stream),
             "update_momentum");
+}
+
+// Weight gradients with the SGD update as the tail of the same launch:
+// the last block to arrive on `ticket` applies the update and zeroes g.
+void wgrad_update_impl(const at::Tensor& x, const at::Tensor& a1,
+                       const at::Tensor& a2, const at::Tensor& dz,
+                       const at::Tensor& dz2, const at::Tensor& dz1,
+                       const at::Tensor& grads, const at::Tensor& params,
+                       const pcnn_opt& opt, const at::Tensor& ticket,
+                       int64_t B, int64_t chunk_imgs, int64_t roles,
+                       int64_t stream, const char* what) {
+  int f = act_flag(x);
+  TORCH_CHECK(dz1.scalar_type() == x.scalar_type(),
+              "dz1 must match the activation dtype");
+  check_flat_buckets(params, grads);
+  check_hip(pcnn_launch_wgrad_update(
+                x.data_ptr(), a1.data_ptr(), a2.data_ptr(),
+                dz.data_ptr<float>(), dz2.data_ptr<float>(), dz1.data_ptr(),
+                grads.data_ptr<float>(), params.data_ptr<float>(), &opt,
+                ticket_ptr(ticket), (int)B, f, (int)chunk_imgs, (int)roles,
+                (void*)stream),
+            what);
+}
+
+void hip_wgrad_update(at::Tensor x, at::Tensor a1, at::Tensor a2,
+                      at::Tensor dz, at::Tensor dz2, at::Tensor dz1,
+                      at::Tensor grads, at::Tensor params, double step,
+                      at::Tensor ticket, int64_t B, int64_t chunk_imgs,
+                      int64_t roles, int64_t stream) {
+  wgrad_update_impl(x, a1, a2, dz, dz2, dz1, grads, params, plain_opt(step),
+                    ticket, B, chunk_imgs, roles, stream, "wgrad_update");
 }
 
 // hip_wgrad_update with the momentum tail (k_wgrad_update_mom).
@@ -352,21 +189,10 @@ void hip_wgrad_update_momentum(at::Tensor x, at::Tensor a1, at::Tensor a2,
                                at::Tensor ticket, int64_t B,
                                int64_t chunk_imgs, int64_t roles,
                                int64_t stream) {
-  int f = act_flag(x);
-  TORCH_CHECK(dz1.scalar_type() == x.scalar_type(),
-              "dz1 must match the activation dtype");
-  TORCH_CHECK(params.is_cuda() && grads.is_cuda() &&
-                  params.numel() == pcnn::N_PARAMS &&
-                  grads.numel() == pcnn::N_PARAMS,
-              "params/grads must be the flat device buckets");
-  check_hip(pcnn_launch_wgrad_update_mom(
-                x.data_ptr(), a1.data_ptr(), a2.data_ptr(),
-                dz.data_ptr<float>(), dz2.data_ptr<float>(), dz1.data_ptr(),
-                grads.data_ptr<float>(), params.data_ptr<float>(),
-                vel_ptr(vel, params), (float)scale, (float)dt, (float)mu,
-                (float)wd, nesterov ? 1 : 0, ticket_ptr(ticket), (int)B, f,
-                (int)chunk_imgs, (int)roles, (void*)stream),
-            "wgrad_update_momentum");
+  wgrad_update_impl(x, a1, a2, dz, dz2, dz1, grads, params,
+                    momentum_opt(vel, params, dt, scale, mu, wd, nesterov),
+                    ticket, B, chunk_imgs, roles, stream,
+                    "wgrad_update_momentum");
 }
 
 float* gslab_ptr(const at::Tensor& gslab, int64_t B) {
@@ -402,7 +228,7 @@ void hip_fwdbwd_inblock(at::Tensor x, at::Tensor params, at::Tensor a2,
                   y.numel() >= B * pcnn::FC_OUT &&
                   dz.numel() >= B * pcnn::FC_OUT && labels.numel() >= B,
               "buffers too small for B");
-  check_hip(pcnn_launch_fwdbwd_inblock_v(
+  check_hip(pcnn_launch_fwdbwd_inblock(
                 x.data_ptr(), params.data_ptr<float>(), a2.data_ptr(),
                 y.data_ptr<float>(), dz.data_ptr<float>(),
                 labels.data_ptr<int>(),
@@ -412,17 +238,20 @@ void hip_fwdbwd_inblock(at::Tensor x, at::Tensor params, at::Tensor a2,
             "fwdbwd_inblock");
 }
 
-// One whole training step with in-block weight grads (k_fwdbwd<INBLOCK> ->
-// k_reduce_update); above _C.INBLOCK_MAX_BATCH the launcher runs
-// k_fwdbwd -> k_wgrad_update instead, which is why it takes every buffer.
-void hip_step_inblock(at::Tensor x, at::Tensor params, at::Tensor a1,
-                      at::Tensor a2, at::Tensor y, at::Tensor dz,
-                      at::Tensor dz2, at::Tensor dz1, at::Tensor labels,
-                      at::Tensor loss_accum, at::Tensor grads,
-                      at::Tensor ticket, at::Tensor gslab, double step,
-                      int64_t B, int64_t chunk_imgs, int64_t stream,
-                      int64_t pool_mode, int64_t loss_mode,
-                      int64_t variant) {
+// One whole training step with in-block weight grads (k_fwdbwd<INBLOCK> or
+// k_fwdbwd_pair -> k_reduce_update[_mom]); above _C.INBLOCK_MAX_BATCH the
+// launcher runs k_fwdbwd -> k_wgrad_update[_mom] instead, which is why it
+// takes every buffer.
+void step_inblock_impl(const at::Tensor& x, const at::Tensor& params,
+                       const at::Tensor& a1, const at::Tensor& a2,
+                       const at::Tensor& y, const at::Tensor& dz,
+                       const at::Tensor& dz2, const at::Tensor& dz1,
+                       const at::Tensor& labels, const at::Tensor& loss_accum,
+                       const at::Tensor& grads, const at::Tensor& ticket,
+                       const at::Tensor& gslab, const pcnn_opt& opt,
+                       int64_t B, int64_t chunk_imgs, int64_t stream,
+                       int64_t pool_mode, int64_t loss_mode, int64_t variant,
+                       const char* what) {
   TORCH_CHECK(x.is_cuda() && params.is_cuda(), "expected device tensors");
   TORCH_CHECK(labels.scalar_type() == at::kInt, "labels must be int32");
   TORCH_CHECK(dz1.scalar_type() == x.scalar_type() &&
@@ -441,15 +270,45 @@ void hip_step_inblock(at::Tensor x, at::Tensor params, at::Tensor a1,
                    dz1.numel() >= B * pcnn::C1_OUT &&
                    dz2.numel() >= B * pcnn::S1_OUT),
               "a1/dz1/dz2 too small for the large-batch path");
-  check_hip(pcnn_launch_step_inblock_v(
+  check_hip(pcnn_launch_step_inblock(
                 x.data_ptr(), params.data_ptr<float>(), a1.data_ptr(),
                 a2.data_ptr(), y.data_ptr<float>(), dz.data_ptr<float>(),
                 dz2.data_ptr<float>(), dz1.data_ptr(), labels.data_ptr<int>(),
                 loss_accum.data_ptr<float>(), grads.data_ptr<float>(),
-                ticket_ptr(ticket), gslab_ptr(gslab, B), (float)step, (int)B,
+                ticket_ptr(ticket), gslab_ptr(gslab, B), &opt, (int)B,
                 act_flag(x), (int)pool_mode, (int)loss_mode, (int)chunk_imgs,
                 inblock_variant(variant), (void*)stream),
-            "step_inblock");
+            what);
+}
+
+void hip_step_inblock(at::Tensor x, at::Tensor params, at::Tensor a1,
+                      at::Tensor a2, at::Tensor y, at::Tensor dz,
+                      at::Tensor dz2, at::Tensor dz1, at::Tensor labels,
+                      at::Tensor loss_accum, at::Tensor grads,
+                      at::Tensor ticket, at::Tensor gslab, double step,
+                      int64_t B, int64_t chunk_imgs, int64_t stream,
+                      int64_t pool_mode, int64_t loss_mode,
+                      int64_t variant) {
+  step_inblock_impl(x, params, a1, a2, y, dz, dz2, dz1, labels, loss_accum,
+                    grads, ticket, gslab, plain_opt(step), B, chunk_imgs,
+                    stream, pool_mode, loss_mode, variant, "step_inblock");
+}
+
+void hip_step_inblock_momentum(at::Tensor x, at::Tensor params,
+                               at::Tensor vel, at::Tensor a1, at::Tensor a2,
+                               at::Tensor y, at::Tensor dz, at::Tensor dz2,
+                               at::Tensor dz1, at::Tensor labels,
+                               at::Tensor loss_accum, at::Tensor grads,
+                               at::Tensor ticket, at::Tensor gslab, double dt,
+                               double scale, double mu, double wd,
+                               bool nesterov, int64_t B, int64_t chunk_imgs,
+                               int64_t stream, int64_t pool_mode,
+                               int64_t loss_mode, int64_t variant) {
+  step_inblock_impl(x, params, a1, a2, y, dz, dz2, dz1, labels, loss_accum,
+                    grads, ticket, gslab,
+                    momentum_opt(vel, params, dt, scale, mu, wd, nesterov), B,
+                    chunk_imgs, stream, pool_mode, loss_mode, variant,
+                    "step_inblock_momentum");
 }
 
 // Second kernel of the in-block step on its own, momentum form
@@ -466,56 +325,12 @@ void hip_reduce_update_momentum(at::Tensor gslab, at::Tensor a2,
                   dz.is_cuda() && dz.scalar_type() == at::kFloat &&
                   dz.numel() >= B * pcnn::FC_OUT,
               "buffers too small for B");
-  check_hip(pcnn_launch_reduce_update_mom(
-                gslab_ptr(gslab, B), a2.data_ptr(), dz.data_ptr<float>(),
-                params.data_ptr<float>(), vel_ptr(vel, params), (float)scale,
-                (float)dt, (float)mu, (float)wd, nesterov ? 1 : 0, (int)B,
-                act_flag(a2), (void*)stream),
+  const pcnn_opt opt = momentum_opt(vel, params, dt, scale, mu, wd, nesterov);
+  check_hip(pcnn_launch_reduce_update(gslab_ptr(gslab, B), a2.data_ptr(),
+                                      dz.data_ptr<float>(),
+                                      params.data_ptr<float>(), &opt, (int)B,
+                                      act_flag(a2), (void*)stream),
             "reduce_update_momentum");
-}
-
-// hip_step_inblock with the momentum update (k_fwdbwd<INBLOCK> ->
-// k_reduce_update_mom; above _C.INBLOCK_MAX_BATCH k_fwdbwd ->
-// k_wgrad_update_mom).
-void hip_step_inblock_momentum(at::Tensor x, at::Tensor params,
-                               at::Tensor vel, at::Tensor a1, at::Tensor a2,
-                               at::Tensor y, at::Tensor dz, at::Tensor dz2,
-                               at::Tensor dz1, at::Tensor labels,
-                               at::Tensor loss_accum, at::Tensor grads,
-                               at::Tensor ticket, at::Tensor gslab, double dt,
-                               double scale, double mu, double wd,
-                               bool nesterov, int64_t B, int64_t chunk_imgs,
-                               int64_t stream, int64_t pool_mode,
-                               int64_t loss_mode, int64_t variant) {
-  TORCH_CHECK(x.is_cuda() && params.is_cuda(), "expected device tensors");
-  TORCH_CHECK(labels.scalar_type() == at::kInt, "labels must be int32");
-  TORCH_CHECK(dz1.scalar_type() == x.scalar_type() &&
-                  a2.scalar_type() == x.scalar_type(),
-              "a2/dz1 must match the activation dtype");
-  TORCH_CHECK(params.numel() == pcnn::N_PARAMS &&
-                  grads.numel() == pcnn::N_PARAMS,
-              "params/grads must be the flat device buckets");
-  TORCH_CHECK(B >= 1 && x.numel() >= B * pcnn::IN_PIX &&
-                  a2.numel() >= B * pcnn::S1_OUT &&
-                  y.numel() >= B * pcnn::FC_OUT &&
-                  dz.numel() >= B * pcnn::FC_OUT && labels.numel() >= B,
-              "buffers too small for B");
-  TORCH_CHECK(B <= pcnn_inblock_max_batch() ||
-                  (a1.numel() >= B * pcnn::C1_OUT &&
-                   dz1.numel() >= B * pcnn::C1_OUT &&
-                   dz2.numel() >= B * pcnn::S1_OUT),
-              "a1/dz1/dz2 too small for the large-batch path");
-  check_hip(pcnn_launch_step_inblock_mom_v(
-                x.data_ptr(), params.data_ptr<float>(), vel_ptr(vel, params),
-                a1.data_ptr(), a2.data_ptr(), y.data_ptr<float>(),
-                dz.data_ptr<float>(), dz2.data_ptr<float>(), dz1.data_ptr(),
-                labels.data_ptr<int>(), loss_accum.data_ptr<float>(),
-                grads.data_ptr<float>(), ticket_ptr(ticket),
-                gslab_ptr(gslab, B), (float)scale, (float)dt, (float)mu,
-                (float)wd, nesterov ? 1 : 0, (int)B, act_flag(x),
-                (int)pool_mode, (int)loss_mode, (int)chunk_imgs,
-                inblock_variant(variant), (void*)stream),
-            "step_inblock_momentum");
 }
 
 // Single-GPU fused training loop: enqueues `steps` full training steps
@@ -540,10 +355,9 @@ void hip_train_steps(at::Tensor x_pool, at::Tensor labels_pool,
   const int var = inblock_variant(variant);
   // a non-empty vel selects the momentum update in every step mode; dt and
   // scale then replace the pre-multiplied step_scale
-  float* vp = vel.numel() ? vel_ptr(vel, params) : nullptr;
-  const float o_scale = (float)scale, o_dt = (float)dt, o_mu = (float)mu,
-              o_wd = (float)wd;
-  const int o_nes = nesterov ? 1 : 0;
+  const pcnn_opt opt =
+      vel.numel() ? momentum_opt(vel, params, dt, scale, mu, wd, nesterov)
+                  : plain_opt(step_scale);
   TORCH_CHECK(step_mode == 3 || step_mode == 2 || step_mode == 4,
               "step_mode must be 3, 2 or 4");
   TORCH_CHECK(step_mode == 3 || !wgrad_fuse,
@@ -570,67 +384,37 @@ void hip_train_steps(at::Tensor x_pool, at::Tensor labels_pool,
     const int64_t i = st % P;
     const void* xb = xp + (size_t)i * B * pcnn::IN_PIX * esz;
     const int* lb = lp + i * B;
-    if (slab != nullptr && vp != nullptr) {
-      check_hip(pcnn_launch_step_inblock_mom_v(
-                    xb, pp, vp, a1.data_ptr(), a2.data_ptr(),
-                    y.data_ptr<float>(), dz.data_ptr<float>(),
-                    dz2.data_ptr<float>(), dz1.data_ptr(), lb,
-                    loss_accum.data_ptr<float>(), gp, tk, slab, o_scale,
-                    o_dt, o_mu, o_wd, o_nes, (int)B, f, (int)pool_mode,
-                    (int)loss_mode, (int)chunk_imgs, var, s),
-                "train_steps/step_inblock_momentum");
-      continue;
-    }
-    if (slab != nullptr) {
-      check_hip(pcnn_launch_step_inblock_v(
+    if (step_mode == 4) {
+      check_hip(pcnn_launch_step_inblock(
                     xb, pp, a1.data_ptr(), a2.data_ptr(), y.data_ptr<float>(),
                     dz.data_ptr<float>(), dz2.data_ptr<float>(),
                     dz1.data_ptr(), lb, loss_accum.data_ptr<float>(), gp, tk,
-                    slab, (float)step_scale, (int)B, f, (int)pool_mode,
-                    (int)loss_mode, (int)chunk_imgs, var, s),
+                    slab, &opt, (int)B, f, (int)pool_mode, (int)loss_mode,
+                    (int)chunk_imgs, var, s),
                 "train_steps/step_inblock");
       continue;
     }
-    check_hip(pcnn_launch_fwdbwd_ex2(xb, pp, a1.data_ptr(), a2.data_ptr(),
-                                     y.data_ptr<float>(),
-                                     dz.data_ptr<float>(),
-                                     dz2.data_ptr<float>(),
-                                     dz1.data_ptr(), lb,
-                                     loss_accum.data_ptr<float>(), nullptr,
-                                     (int)B, f, 0, (int)pool_mode,
-                                     (int)loss_mode, gp, (int)wgrad_fuse, s),
+    check_hip(pcnn_launch_fwdbwd(xb, pp, a1.data_ptr(), a2.data_ptr(),
+                                 y.data_ptr<float>(), dz.data_ptr<float>(),
+                                 dz2.data_ptr<float>(), dz1.data_ptr(), lb,
+                                 loss_accum.data_ptr<float>(), nullptr,
+                                 (int)B, f, 0, (int)pool_mode, (int)loss_mode,
+                                 gp, (int)wgrad_fuse, s),
               "train_steps/fwdbwd");
-    if (tk != nullptr && vp != nullptr) {
-      check_hip(pcnn_launch_wgrad_update_mom(
-                    xb, a1.data_ptr(), a2.data_ptr(), dz.data_ptr<float>(),
-                    dz2.data_ptr<float>(), dz1.data_ptr(), gp, pp, vp,
-                    o_scale, o_dt, o_mu, o_wd, o_nes, tk, (int)B, f,
-                    (int)chunk_imgs, wroles, s),
-                "train_steps/wgrad_update_momentum");
-      continue;
-    }
-    if (tk != nullptr) {
+    if (step_mode == 2) {
       check_hip(pcnn_launch_wgrad_update(
                     xb, a1.data_ptr(), a2.data_ptr(), dz.data_ptr<float>(),
-                    dz2.data_ptr<float>(), dz1.data_ptr(), gp, pp,
-                    (float)step_scale, tk, (int)B, f, (int)chunk_imgs, wroles,
-                    s),
+                    dz2.data_ptr<float>(), dz1.data_ptr(), gp, pp, &opt, tk,
+                    (int)B, f, (int)chunk_imgs, wroles, s),
                 "train_steps/wgrad_update");
       continue;
     }
-    check_hip(pcnn_launch_wgrad_ex(xb, a1.data_ptr(), a2.data_ptr(),
-                                   dz.data_ptr<float>(), dz2.data_ptr<float>(),
-                                   dz1.data_ptr(), gp, (int)B, f,
-                                   (int)chunk_imgs, wroles, s),
+    check_hip(pcnn_launch_wgrad(xb, a1.data_ptr(), a2.data_ptr(),
+                                dz.data_ptr<float>(), dz2.data_ptr<float>(),
+                                dz1.data_ptr(), gp, (int)B, f,
+                                (int)chunk_imgs, wroles, s),
               "train_steps/wgrad");
-    if (vp != nullptr) {
-      check_hip(pcnn_launch_update_mom(pp, gp, vp, o_scale, o_dt, o_mu, o_wd,
-                                       o_nes, s),
-                "train_steps/update_momentum");
-      continue;
-    }
-    check_hip(pcnn_launch_update(pp, gp, (float)step_scale, s),
-              "train_steps/update");
+    check_hip(pcnn_launch_update(pp, gp, &opt, s), "train_steps/update");
   }
 }
 
@@ -652,7 +436,7 @@ void deep_gemm(at::Tensor A, at::Tensor Bsrc, at::Tensor bias, at::Tensor C,
                at::Tensor Bpre, at::Tensor imx, int64_t XH, int64_t XW,
                int64_t XC, int64_t XK, int64_t XP, at::Tensor epi,
                at::Tensor pw, at::Tensor pout, int64_t PK, at::Tensor c32) {
-  check_hip(pcnn_deep_gemm_ex4(
+  check_hip(pcnn_deep_gemm(
                 A.data_ptr(), Bsrc.data_ptr<float>(),
                 Bpre.numel() ? Bpre.data_ptr() : nullptr,
                 bias.numel() ? bias.data_ptr<float>() : nullptr,
@@ -676,6 +460,41 @@ void deep_cast_wt(at::Tensor W, at::Tensor out, at::Tensor outT, int64_t R,
             "deep_cast_wt");
 }
 
+// The per-stage descriptor lists of the batched weight cast as the launchers
+// take them (pcnn_cast_desc points into this object).
+struct CastDesc {
+  int R[8], C[8], K[8], Cin[8];
+  long long w_off[8], bf_off[8], bfT_off[8], rot_off[8], p8_off[8];
+  pcnn_cast_desc d;
+
+  CastDesc(const char* what, const std::vector<int64_t>& Rv,
+           const std::vector<int64_t>& Cv, const std::vector<int64_t>& Kv,
+           const std::vector<int64_t>& Cinv, const std::vector<int64_t>& w,
+           const std::vector<int64_t>& bf, const std::vector<int64_t>& bfT,
+           const std::vector<int64_t>& rot, const std::vector<int64_t>& p8) {
+    const size_t n = Rv.size();
+    TORCH_CHECK(n >= 1 && n <= 8, what, ": 1..8 stages");
+    TORCH_CHECK(Cv.size() == n && Kv.size() == n && Cinv.size() == n &&
+                    w.size() == n && bf.size() == n && bfT.size() == n &&
+                    rot.size() == n && (p8.empty() || p8.size() == n),
+                what, ": descriptor length mismatch");
+    for (size_t s = 0; s < n; ++s) {
+      R[s] = (int)Rv[s];
+      C[s] = (int)Cv[s];
+      K[s] = (int)Kv[s];
+      Cin[s] = (int)Cinv[s];
+      w_off[s] = w[s];
+      bf_off[s] = bf[s];
+      bfT_off[s] = bfT[s];
+      rot_off[s] = rot[s];
+      p8_off[s] = p8.empty() ? -1 : p8[s];
+    }
+    d = pcnn_cast_desc{(int)n,  R,       C,      K,      Cin,
+                       w_off,   bf_off,  bfT_off, rot_off, p8_off};
+  }
+  CastDesc(const CastDesc&) = delete;
+};
+
 void deep_cast_all(at::Tensor params, at::Tensor wbuf,
                    std::vector<int64_t> R, std::vector<int64_t> C,
                    std::vector<int64_t> K, std::vector<int64_t> Cin,
@@ -683,29 +502,10 @@ void deep_cast_all(at::Tensor params, at::Tensor wbuf,
                    std::vector<int64_t> bfT_off,
                    std::vector<int64_t> rot_off,
                    std::vector<int64_t> p8_off, int64_t stream) {
-  const size_t n = R.size();
-  TORCH_CHECK(n >= 1 && n <= 8, "deep_cast_all: 1..8 stages");
-  TORCH_CHECK(C.size() == n && K.size() == n && Cin.size() == n &&
-                  w_off.size() == n && bf_off.size() == n &&
-                  bfT_off.size() == n && rot_off.size() == n &&
-                  (p8_off.empty() || p8_off.size() == n),
-              "deep_cast_all: descriptor length mismatch");
-  int Ri[8], Ci[8], Ki[8], Cini[8];
-  long long wo[8], bo[8], bto[8], ro[8], po[8];
-  for (size_t s = 0; s < n; ++s) {
-    Ri[s] = (int)R[s];
-    Ci[s] = (int)C[s];
-    Ki[s] = (int)K[s];
-    Cini[s] = (int)Cin[s];
-    wo[s] = w_off[s];
-    bo[s] = bf_off[s];
-    bto[s] = bfT_off[s];
-    ro[s] = rot_off[s];
-    po[s] = p8_off.empty() ? -1 : p8_off[s];
-  }
+  const CastDesc cd("deep_cast_all", R, C, K, Cin, w_off, bf_off, bfT_off,
+                    rot_off, p8_off);
   check_hip(pcnn_deep_cast_all(params.data_ptr<float>(), wbuf.data_ptr(),
-                               (int)n, Ri, Ci, Ki, Cini, wo, bo, bto, ro,
-                               po, (void*)stream),
+                               &cd.d, (void*)stream),
             "deep_cast_all");
 }
 
@@ -717,25 +517,12 @@ void deep_update_cast(at::Tensor params, at::Tensor grads, double step,
                       std::vector<int64_t> bfT_off,
                       std::vector<int64_t> rot_off,
                       std::vector<int64_t> p8_off, int64_t stream) {
-  const size_t n = R.size();
-  TORCH_CHECK(n >= 1 && n <= 8, "deep_update_cast: 1..8 stages");
-  int Ri[8], Ci[8], Ki[8], Cini[8];
-  long long wo[8], bo[8], bto[8], ro[8], po[8];
-  for (size_t s = 0; s < n; ++s) {
-    Ri[s] = (int)R[s];
-    Ci[s] = (int)C[s];
-    Ki[s] = (int)K[s];
-    Cini[s] = (int)Cin[s];
-    wo[s] = w_off[s];
-    bo[s] = bf_off[s];
-    bto[s] = bfT_off[s];
-    ro[s] = rot_off[s];
-    po[s] = p8_off.empty() ? -1 : p8_off[s];
-  }
+  const CastDesc cd("deep_update_cast", R, C, K, Cin, w_off, bf_off, bfT_off,
+                    rot_off, p8_off);
+  const pcnn_opt opt = plain_opt(step);
   check_hip(pcnn_deep_update_cast(params.data_ptr<float>(),
                                   grads.data_ptr<float>(), params.numel(),
-                                  (float)step, wbuf.data_ptr(), (int)n, Ri,
-                                  Ci, Ki, Cini, wo, bo, bto, ro, po,
+                                  &opt, wbuf.data_ptr(), &cd.d,
                                   (void*)stream),
             "deep_update_cast");
 }
@@ -753,33 +540,14 @@ void deep_update_cast_momentum(at::Tensor params, at::Tensor grads,
                                std::vector<int64_t> bfT_off,
                                std::vector<int64_t> rot_off,
                                std::vector<int64_t> p8_off, int64_t stream) {
-  const size_t n = R.size();
-  TORCH_CHECK(n >= 1 && n <= 8, "deep_update_cast_momentum: 1..8 stages");
-  TORCH_CHECK(C.size() == n && K.size() == n && Cin.size() == n &&
-                  w_off.size() == n && bf_off.size() == n &&
-                  bfT_off.size() == n && rot_off.size() == n &&
-                  (p8_off.empty() || p8_off.size() == n),
-              "deep_update_cast_momentum: descriptor length mismatch");
+  const CastDesc cd("deep_update_cast_momentum", R, C, K, Cin, w_off, bf_off,
+                    bfT_off, rot_off, p8_off);
   TORCH_CHECK(grads.numel() == params.numel(), "grads/params size mismatch");
-  int Ri[8], Ci[8], Ki[8], Cini[8];
-  long long wo[8], bo[8], bto[8], ro[8], po[8];
-  for (size_t s = 0; s < n; ++s) {
-    Ri[s] = (int)R[s];
-    Ci[s] = (int)C[s];
-    Ki[s] = (int)K[s];
-    Cini[s] = (int)Cin[s];
-    wo[s] = w_off[s];
-    bo[s] = bf_off[s];
-    bto[s] = bfT_off[s];
-    ro[s] = rot_off[s];
-    po[s] = p8_off.empty() ? -1 : p8_off[s];
-  }
-  check_hip(pcnn_deep_update_cast_mom(
-                params.data_ptr<float>(), grads.data_ptr<float>(),
-                vel_ptr(vel, params), params.numel(), (float)scale, (float)dt,
-                (float)mu, (float)wd, nesterov ? 1 : 0, wbuf.data_ptr(),
-                (int)n, Ri, Ci, Ki, Cini, wo, bo, bto, ro, po,
-                (void*)stream),
+  const pcnn_opt opt = momentum_opt(vel, params, dt, scale, mu, wd, nesterov);
+  check_hip(pcnn_deep_update_cast(params.data_ptr<float>(),
+                                  grads.data_ptr<float>(), params.numel(),
+                                  &opt, wbuf.data_ptr(), &cd.d,
+                                  (void*)stream),
             "deep_update_cast_momentum");
 }
 
@@ -847,7 +615,7 @@ void deep_wgrad_gemm(at::Tensor cols, at::Tensor dpre, at::Tensor dW,
     TORCH_CHECK(part.numel() >= MS * KcP * N, "wgrad slab scratch too small");
     pp = part.data_ptr<float>();
   }
-  check_hip(pcnn_deep_wgrad_gemm_ex2(
+  check_hip(pcnn_deep_wgrad_gemm(
                 cols.data_ptr(), dpre.data_ptr(), dW.data_ptr<float>(), pp, M,
                 (int)KcP, (int)N, (int)MS,
                 imx.numel() ? imx.data_ptr() : nullptr, (int)XH, (int)XW,
@@ -922,7 +690,7 @@ void deep_fc_fwd(at::Tensor flat, at::Tensor fw, at::Tensor fb,
                  at::Tensor loss_accum, at::Tensor correct_accum, int64_t B,
                  int64_t FCIN, int64_t NCLS, int64_t mode, int64_t stream,
                  at::Tensor dflat) {
-  check_hip(pcnn_deep_fc_fwd2(
+  check_hip(pcnn_deep_fc_fwd(
                 flat.data_ptr(), fw.data_ptr<float>(), fb.data_ptr<float>(),
                 labels.data_ptr<int>(),
                 y.numel() ? y.data_ptr<float>() : nullptr,
@@ -958,9 +726,10 @@ void deep_fc_wgrad(at::Tensor dz, at::Tensor flat, at::Tensor gfw,
 
 void deep_update(at::Tensor params, at::Tensor grads, double step,
                  int64_t stream) {
+  const pcnn_opt opt = plain_opt(step);
   check_hip(pcnn_deep_update(params.data_ptr<float>(),
-                             grads.data_ptr<float>(), params.numel(),
-                             (float)step, (void*)stream),
+                             grads.data_ptr<float>(), params.numel(), &opt,
+                             (void*)stream),
             "deep_update");
 }
 
@@ -968,11 +737,10 @@ void deep_update_momentum(at::Tensor params, at::Tensor grads,
                           at::Tensor vel, double dt, double scale, double mu,
                           double wd, bool nesterov, int64_t stream) {
   TORCH_CHECK(grads.numel() == params.numel(), "grads/params size mismatch");
-  check_hip(pcnn_deep_update_mom(params.data_ptr<float>(),
-                                 grads.data_ptr<float>(),
-                                 vel_ptr(vel, params), params.numel(),
-                                 (float)scale, (float)dt, (float)mu,
-                                 (float)wd, nesterov ? 1 : 0, (void*)stream),
+  const pcnn_opt opt = momentum_opt(vel, params, dt, scale, mu, wd, nesterov);
+  check_hip(pcnn_deep_update(params.data_ptr<float>(),
+                             grads.data_ptr<float>(), params.numel(), &opt,
+                             (void*)stream),
             "deep_update_momentum");
 }
 

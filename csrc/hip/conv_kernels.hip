@@ -29,11 +29,15 @@
 #include <type_traits>
 
 #include "../lenet_dims.h"
+#include "../pcnn_launch.h"
+#include "act_dispatch.h"
 
 namespace pcnn_deep {
 
 using bf16 = __hip_bfloat16;
 using fp16 = __half;
+
+#include "sgd_update.h"
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
@@ -1858,6 +1862,7 @@ struct CastDescs {
                                // x8 input via the implicit fast path)
   long long cum[9];            // cumulative R*C
 };
+
 __global__ void k_cast_wt_all(const float* __restrict__ params,
                               __bf16* __restrict__ wbuf, CastDescs d) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1886,19 +1891,24 @@ __global__ void k_cast_wt_all(const float* __restrict__ params,
 }
 
 // SGD update FUSED with the weight pre-cast: one pass updates every
-// parameter (p += step*g; g = 0) and, for conv-weight elements, emits
-// the next step's bf16 images (wbf/wbfT/wrot/wp8) from the freshly
-// computed value — the separate k_cast_wt_all launch at the next
+// parameter (sgd_apply1: plain or momentum, g = 0) and, for conv-weight
+// elements, emits the next step's bf16 images (wbf/wbfT/wrot/wp8) from the
+// freshly computed value — the separate k_cast_wt_all launch at the next
 // forward is skipped (the engine tracks freshness).
+//
+// The emission block stays written out in k_cast_wt_all and in these two
+// kernels.  Behind a shared __device__ function, or with the two kernels as
+// wrappers of one body that takes the descriptors, the compiler addresses
+// CastDescs differently: k_cast_wt_all went from 23 to 25 VGPRs and both
+// update kernels from 29 to 34 SGPRs.  Only the update rule is shared.
 __global__ void k_update_cast_all(float* __restrict__ params,
                                   float* __restrict__ grads, long long n,
                                   float step, __bf16* __restrict__ wbuf,
                                   CastDescs d) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float pnew = params[i] + step * grads[i];
-  params[i] = pnew;
-  grads[i] = 0.f;
+  const float pnew =
+      sgd_apply1<false>(params, grads, (float*)nullptr, i, step, MomArgs{});
   for (int s = 0; s < d.n; ++s) {
     const long long q = i - d.w_off[s];
     if (q < 0 || q >= d.cum[s + 1] - d.cum[s]) continue;
@@ -1922,33 +1932,6 @@ __global__ void k_update_cast_all(float* __restrict__ params,
   }
 }
 
-// Generic SGD apply + zero:  p += step*g; g = 0  over n params.
-__global__ void k_update_n(float* __restrict__ params,
-                           float* __restrict__ grads, long long n,
-                           float step) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    params[i] += step * grads[i];
-    grads[i] = 0.f;
-  }
-}
-
-// Momentum / Nesterov / weight-decay update (ascent convention):
-//   u = scale*g - wd*p;  v = mu*v + u;  p += dt*v   (nesterov: dt*(u+mu*v))
-// vel is the fp32 velocity bucket in the params layout.  A conv-weight pad
-// row has p = g = v = 0 and stays there under these formulas.
-struct MomArgs {
-  float scale, dt, mu, wd;
-  int nesterov;
-};
-
-__device__ __forceinline__ float mom_apply(float p, float g, float& v,
-                                           const MomArgs& o) {
-  const float u = o.scale * g - o.wd * p;
-  v = o.mu * v + u;
-  return p + o.dt * (o.nesterov ? u + o.mu * v : v);
-}
-
 // k_update_cast_all with the momentum update: the bf16 images are cast
 // from the post-momentum value.
 __global__ void k_update_cast_all_mom(float* __restrict__ params,
@@ -1958,46 +1941,52 @@ __global__ void k_update_cast_all_mom(float* __restrict__ params,
                                       CastDescs d) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  float v = vel[i];
-  const float pnew = mom_apply(params[i], grads[i], v, o);
-  params[i] = pnew;
-  vel[i] = v;
-  grads[i] = 0.f;
+  const float pnew = sgd_apply1<true>(params, grads, vel, i, 0.f, o);
   for (int s = 0; s < d.n; ++s) {
     const long long q = i - d.w_off[s];
     if (q < 0 || q >= d.cum[s + 1] - d.cum[s]) continue;
     const int C = d.C[s];
     const int kc = (int)(q / C);
     const int c = (int)(q - (long long)kc * C);
-    const __bf16 bv = (__bf16)pnew;
-    wbuf[d.bf_off[s] + q] = bv;
-    wbuf[d.bfT_off[s] + (long long)c * d.R[s] + kc] = bv;
+    const __bf16 v = (__bf16)pnew;
+    wbuf[d.bf_off[s] + q] = v;
+    wbuf[d.bfT_off[s] + (long long)c * d.R[s] + kc] = v;
     const int Cin = d.Cin[s], K = d.K[s];
     if (kc < K * K * Cin) {
       const int ci = kc % Cin;
       const int p2 = kc / Cin;
       const int ki = p2 / K, kj = p2 - ki * K;
       const int col = ((K - 1 - ki) * K + (K - 1 - kj)) * C + c;
-      wbuf[d.rot_off[s] + (long long)ci * (K * K * C) + col] = bv;
+      wbuf[d.rot_off[s] + (long long)ci * (K * K * C) + col] = v;
       if (d.p8_off[s] >= 0)
-        wbuf[d.p8_off[s] + (long long)c * (K * K * 8) + p2 * 8 + ci] = bv;
+        wbuf[d.p8_off[s] + (long long)c * (K * K * 8) + p2 * 8 + ci] = v;
     }
     break;
   }
 }
 
-// k_update_n with the momentum update.
+// Generic SGD apply + zero over n params (sgd_apply1).
+template <bool MOM>
+__device__ __forceinline__ void update_n_body(float* __restrict__ params,
+                                              float* __restrict__ grads,
+                                              float* __restrict__ vel,
+                                              long long n, float step,
+                                              const MomArgs& o) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) sgd_apply1<MOM>(params, grads, vel, i, step, o);
+}
+
+__global__ void k_update_n(float* __restrict__ params,
+                           float* __restrict__ grads, long long n,
+                           float step) {
+  update_n_body<false>(params, grads, nullptr, n, step, MomArgs{});
+}
+
 __global__ void k_update_n_mom(float* __restrict__ params,
                                float* __restrict__ grads,
                                float* __restrict__ vel, long long n,
                                MomArgs o) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    float v = vel[i];
-    params[i] = mom_apply(params[i], grads[i], v, o);
-    vel[i] = v;
-    grads[i] = 0.f;
-  }
+  update_n_body<true>(params, grads, vel, n, 0.f, o);
 }
 
 // MFMA layout self-test: D[16][16] = A[16][32] @ B[32][16], plain fp32 I/O.
@@ -2021,23 +2010,10 @@ __global__ void k_mfma_selftest(const float* __restrict__ A,
 }  // namespace pcnn_deep
 
 // ---------------------------------------------------------------------------
-// extern "C" launchers.  act flag: 0 = fp32, 1 = bf16, 2 = fp16.
+// extern "C" launchers, declared in ../pcnn_launch.h.  act flag: 0 = fp32,
+// 1 = bf16, 2 = fp16.
 // ---------------------------------------------------------------------------
 using namespace pcnn_deep;
-
-#define PCNN_DISPATCH(flag, ...)                    \
-  do {                                               \
-    if ((flag) == 1) {                               \
-      using act_t = bf16;                            \
-      __VA_ARGS__;                                   \
-    } else if ((flag) == 2) {                        \
-      using act_t = fp16;                            \
-      __VA_ARGS__;                                   \
-    } else {                                         \
-      using act_t = float;                           \
-      __VA_ARGS__;                                   \
-    }                                                \
-  } while (0)
 
 extern "C" {
 
@@ -2066,7 +2042,7 @@ int pcnn_deep_im2col(const void* x, void* cols, int B, int H, int W, int Cin,
   return (int)hipGetLastError();
 }
 
-int pcnn_deep_gemm_ex4(const void* A, const float* Bsrc, const void* Bpre,
+int pcnn_deep_gemm(const void* A, const float* Bsrc, const void* Bpre,
                        const float* bias, void* C, long long M, int K, int N,
                        int ldA, int ldC, int b_kxn, int epilogue,
                        const void* imx, int XH, int XW, int XC, int XK,
@@ -2146,35 +2122,6 @@ int pcnn_deep_gemm_ex4(const void* A, const float* Bsrc, const void* Bpre,
   return (int)hipGetLastError();
 }
 
-int pcnn_deep_gemm_ex3(const void* A, const float* Bsrc, const void* Bpre,
-                       const float* bias, void* C, long long M, int K, int N,
-                       int ldA, int ldC, int b_kxn, int epilogue,
-                       const void* imx, int XH, int XW, int XC, int XK,
-                       int XP, const void* epi, const float* pw, void* pout,
-                       int PK, int actf, void* stream) {
-  return pcnn_deep_gemm_ex4(A, Bsrc, Bpre, bias, C, M, K, N, ldA, ldC,
-                            b_kxn, epilogue, imx, XH, XW, XC, XK, XP, epi,
-                            pw, pout, PK, nullptr, 0, actf, stream);
-}
-
-int pcnn_deep_gemm_ex(const void* A, const float* Bsrc, const void* Bpre,
-                      const float* bias, void* C, long long M, int K, int N,
-                      int ldA, int ldC, int b_kxn, int epilogue,
-                      const void* imx, int XH, int XW, int XC, int XK,
-                      int XP, int actf, void* stream) {
-  return pcnn_deep_gemm_ex3(A, Bsrc, Bpre, bias, C, M, K, N, ldA, ldC,
-                            b_kxn, epilogue, imx, XH, XW, XC, XK, XP,
-                            nullptr, nullptr, nullptr, 0, actf, stream);
-}
-
-int pcnn_deep_gemm(const void* A, const float* Bsrc, const float* bias,
-                   void* C, long long M, int K, int N, int ldA, int ldC,
-                   int b_kxn, int epilogue, int actf, void* stream) {
-  return pcnn_deep_gemm_ex(A, Bsrc, nullptr, bias, C, M, K, N, ldA, ldC,
-                           b_kxn, epilogue, nullptr, 0, 0, 0, 0, 0, actf,
-                           stream);
-}
-
 int pcnn_deep_cast_wt(const float* W, void* out, void* outT, int R, int C,
                       void* stream) {
   const long long total = (long long)R * C;
@@ -2184,110 +2131,58 @@ int pcnn_deep_cast_wt(const float* W, void* out, void* outT, int R, int C,
   return (int)hipGetLastError();
 }
 
-int pcnn_deep_cast_all(const float* params, void* wbuf, int n_stages,
-                       const int* R, const int* C, const int* K,
-                       const int* Cin, const long long* w_off,
-                       const long long* bf_off, const long long* bfT_off,
-                       const long long* rot_off, const long long* p8_off,
-                       void* stream) {
-  if (n_stages < 1 || n_stages > 8) return -2;
-  CastDescs d;
-  d.n = n_stages;
+// Kernel-argument form of the caller's per-stage arrays; false if refused.
+static bool fill_cast_descs(const pcnn_cast_desc* desc, CastDescs& d) {
+  if (desc == nullptr || desc->n_stages < 1 || desc->n_stages > 8)
+    return false;
+  d.n = desc->n_stages;
   d.cum[0] = 0;
-  for (int s = 0; s < n_stages; ++s) {
-    d.R[s] = R[s];
-    d.C[s] = C[s];
-    d.K[s] = K[s];
-    d.Cin[s] = Cin[s];
-    d.w_off[s] = w_off[s];
-    d.bf_off[s] = bf_off[s];
-    d.bfT_off[s] = bfT_off[s];
-    d.rot_off[s] = rot_off[s];
-    d.p8_off[s] = p8_off ? p8_off[s] : -1;
-    d.cum[s + 1] = d.cum[s] + (long long)R[s] * C[s];
+  for (int s = 0; s < d.n; ++s) {
+    d.R[s] = desc->R[s];
+    d.C[s] = desc->C[s];
+    d.K[s] = desc->K[s];
+    d.Cin[s] = desc->Cin[s];
+    d.w_off[s] = desc->w_off[s];
+    d.bf_off[s] = desc->bf_off[s];
+    d.bfT_off[s] = desc->bfT_off[s];
+    d.rot_off[s] = desc->rot_off[s];
+    d.p8_off[s] = desc->p8_off ? desc->p8_off[s] : -1;
+    d.cum[s + 1] = d.cum[s] + (long long)d.R[s] * d.C[s];
   }
-  dim3 grid((unsigned)((d.cum[n_stages] + 255) / 256)), block(256);
+  return true;
+}
+
+int pcnn_deep_cast_all(const float* params, void* wbuf,
+                       const pcnn_cast_desc* desc, void* stream) {
+  CastDescs d;
+  if (!fill_cast_descs(desc, d)) return -2;
+  dim3 grid((unsigned)((d.cum[d.n] + 255) / 256)), block(256);
   hipLaunchKernelGGL(k_cast_wt_all, grid, block, 0, (hipStream_t)stream,
                      params, (__bf16*)wbuf, d);
   return (int)hipGetLastError();
 }
 
+// SGD update + weight pre-cast (k_update_cast_all, or k_update_cast_all_mom
+// when opt->vel is set: the images are then cast from the post-momentum
+// value).
 int pcnn_deep_update_cast(float* params, float* grads, long long n,
-                          float step, void* wbuf, int n_stages, const int* R,
-                          const int* C, const int* K, const int* Cin,
-                          const long long* w_off, const long long* bf_off,
-                          const long long* bfT_off, const long long* rot_off,
-                          const long long* p8_off, void* stream) {
-  if (n_stages < 1 || n_stages > 8) return -2;
+                          const pcnn_opt* opt, void* wbuf,
+                          const pcnn_cast_desc* desc, void* stream) {
   CastDescs d;
-  d.n = n_stages;
-  d.cum[0] = 0;
-  for (int s2 = 0; s2 < n_stages; ++s2) {
-    d.R[s2] = R[s2];
-    d.C[s2] = C[s2];
-    d.K[s2] = K[s2];
-    d.Cin[s2] = Cin[s2];
-    d.w_off[s2] = w_off[s2];
-    d.bf_off[s2] = bf_off[s2];
-    d.bfT_off[s2] = bfT_off[s2];
-    d.rot_off[s2] = rot_off[s2];
-    d.p8_off[s2] = p8_off ? p8_off[s2] : -1;
-    d.cum[s2 + 1] = d.cum[s2] + (long long)R[s2] * C[s2];
-  }
+  if (opt == nullptr || !fill_cast_descs(desc, d)) return -2;
   dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  hipLaunchKernelGGL(k_update_cast_all, grid, block, 0,
-                     (hipStream_t)stream, params, grads, n, step,
-                     (__bf16*)wbuf, d);
+  if (opt->vel != nullptr)
+    hipLaunchKernelGGL(k_update_cast_all_mom, grid, block, 0,
+                       (hipStream_t)stream, params, grads, opt->vel, n,
+                       mom_args(opt), (__bf16*)wbuf, d);
+  else
+    hipLaunchKernelGGL(k_update_cast_all, grid, block, 0,
+                       (hipStream_t)stream, params, grads, n, opt->step,
+                       (__bf16*)wbuf, d);
   return (int)hipGetLastError();
 }
 
-// pcnn_deep_update_cast with the momentum update (k_update_cast_all_mom);
-// scale and dt are passed apart, vel is the fp32 velocity bucket [n].
-int pcnn_deep_update_cast_mom(float* params, float* grads, float* vel,
-                              long long n, float scale, float dt, float mu,
-                              float wd, int nesterov, void* wbuf,
-                              int n_stages, const int* R, const int* C,
-                              const int* K, const int* Cin,
-                              const long long* w_off, const long long* bf_off,
-                              const long long* bfT_off,
-                              const long long* rot_off,
-                              const long long* p8_off, void* stream) {
-  if (n_stages < 1 || n_stages > 8 || vel == nullptr) return -2;
-  CastDescs d;
-  d.n = n_stages;
-  d.cum[0] = 0;
-  for (int s2 = 0; s2 < n_stages; ++s2) {
-    d.R[s2] = R[s2];
-    d.C[s2] = C[s2];
-    d.K[s2] = K[s2];
-    d.Cin[s2] = Cin[s2];
-    d.w_off[s2] = w_off[s2];
-    d.bf_off[s2] = bf_off[s2];
-    d.bfT_off[s2] = bfT_off[s2];
-    d.rot_off[s2] = rot_off[s2];
-    d.p8_off[s2] = p8_off ? p8_off[s2] : -1;
-    d.cum[s2 + 1] = d.cum[s2] + (long long)R[s2] * C[s2];
-  }
-  const MomArgs o{scale, dt, mu, wd, nesterov};
-  dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  hipLaunchKernelGGL(k_update_cast_all_mom, grid, block, 0,
-                     (hipStream_t)stream, params, grads, vel, n, o,
-                     (__bf16*)wbuf, d);
-  return (int)hipGetLastError();
-}
-
-int pcnn_deep_update_mom(float* params, float* grads, float* vel, long long n,
-                         float scale, float dt, float mu, float wd,
-                         int nesterov, void* stream) {
-  if (vel == nullptr) return -2;
-  const MomArgs o{scale, dt, mu, wd, nesterov};
-  dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  hipLaunchKernelGGL(k_update_n_mom, grid, block, 0, (hipStream_t)stream,
-                     params, grads, vel, n, o);
-  return (int)hipGetLastError();
-}
-
-int pcnn_deep_wgrad_gemm_ex2(const void* cols, const void* dpre, float* dW,
+int pcnn_deep_wgrad_gemm(const void* cols, const void* dpre, float* dW,
                              float* part, long long M, int KcP, int N,
                              int MS, const void* imx, int XH, int XW, int XC,
                              int XK, int XP, float* db, int actf,
@@ -2316,14 +2211,6 @@ int pcnn_deep_wgrad_gemm_ex2(const void* cols, const void* dpre, float* dW,
                        total, MS);
   }
   return (int)hipGetLastError();
-}
-
-int pcnn_deep_wgrad_gemm_ex(const void* cols, const void* dpre, float* dW,
-                            float* part, long long M, int KcP, int N, int MS,
-                            const void* imx, int XH, int XW, int XC, int XK,
-                            int XP, int actf, void* stream) {
-  return pcnn_deep_wgrad_gemm_ex2(cols, dpre, dW, part, M, KcP, N, MS, imx,
-                                  XH, XW, XC, XK, XP, nullptr, actf, stream);
 }
 
 // n_stages wgrad GEMMs in one launch (see k_wgrad_multi).  a[s] is the
@@ -2391,13 +2278,6 @@ int pcnn_deep_remap_dw8(float* dW8, float* dW, int KK, int Cin, int Cout,
   hipLaunchKernelGGL(k_remap_dw8, grid, block, 0, (hipStream_t)stream, dW8,
                      dW, KK, Cin, Cout);
   return (int)hipGetLastError();
-}
-
-int pcnn_deep_wgrad_gemm(const void* cols, const void* dpre, float* dW,
-                         float* part, long long M, int KcP, int N, int MS,
-                         int actf, void* stream) {
-  return pcnn_deep_wgrad_gemm_ex(cols, dpre, dW, part, M, KcP, N, MS, nullptr,
-                                 0, 0, 0, 0, 0, actf, stream);
 }
 
 int pcnn_deep_colsum(const void* dpre, float* part, float* db, long long M,
@@ -2503,7 +2383,7 @@ int pcnn_deep_pool_wbwd(const void* dppre, const void* a, const float* pw,
   return (int)hipGetLastError();
 }
 
-int pcnn_deep_fc_fwd2(const void* flat, const float* fw, const float* fb,
+int pcnn_deep_fc_fwd(const void* flat, const float* fw, const float* fb,
                       const int* labels, float* yg, float* dzg,
                       float* loss_accum, int* correct_accum, int B, int FCIN,
                       int NCLS, int mode, void* dflat, int actf,
@@ -2516,15 +2396,6 @@ int pcnn_deep_fc_fwd2(const void* flat, const float* fw, const float* fb,
                                           B, FCIN, NCLS, mode,
                                           (act_t*)dflat));
   return (int)hipGetLastError();
-}
-
-int pcnn_deep_fc_fwd(const void* flat, const float* fw, const float* fb,
-                     const int* labels, float* yg, float* dzg,
-                     float* loss_accum, int* correct_accum, int B, int FCIN,
-                     int NCLS, int mode, int actf, void* stream) {
-  return pcnn_deep_fc_fwd2(flat, fw, fb, labels, yg, dzg, loss_accum,
-                           correct_accum, B, FCIN, NCLS, mode, nullptr,
-                           actf, stream);
 }
 
 int pcnn_deep_fc_bwd(const float* dzg, const void* flat, const float* fw,
@@ -2552,11 +2423,16 @@ int pcnn_deep_fc_wgrad(const float* dzg, const void* flat, float* gfw,
   return (int)hipGetLastError();
 }
 
-int pcnn_deep_update(float* params, float* grads, long long n, float step,
-                     void* stream) {
+int pcnn_deep_update(float* params, float* grads, long long n,
+                     const pcnn_opt* opt, void* stream) {
+  if (opt == nullptr) return -2;
   dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  hipLaunchKernelGGL(k_update_n, grid, block, 0, (hipStream_t)stream, params,
-                     grads, n, step);
+  if (opt->vel != nullptr)
+    hipLaunchKernelGGL(k_update_n_mom, grid, block, 0, (hipStream_t)stream,
+                       params, grads, opt->vel, n, mom_args(opt));
+  else
+    hipLaunchKernelGGL(k_update_n, grid, block, 0, (hipStream_t)stream,
+                       params, grads, n, opt->step);
   return (int)hipGetLastError();
 }
 

@@ -58,7 +58,8 @@
 //
 // Every kernel that applies the update (k_update, k_wgrad_update,
 // k_reduce_update) has a _mom twin with momentum / Nesterov / weight decay
-// and an fp32 velocity bucket (mom_apply); the plain kernels are what runs
+// and an fp32 velocity bucket; the two are instantiations of one body with a
+// compile-time MOM flag (sgd_update.h), and the plain kernels are what runs
 // when the optimizer is the default one.
 //
 // Numerics: activations AND the large conv preact gradient (dz1) are
@@ -75,11 +76,15 @@
 #include <hip/hip_runtime.h>
 
 #include "../lenet_dims.h"
+#include "../pcnn_launch.h"
+#include "act_dispatch.h"
 
 namespace pcnn {
 
 using bf16 = __hip_bfloat16;
 using fp16 = __half;
+
+#include "sgd_update.h"
 
 __device__ __forceinline__ float sigmoidf_dev(float v) {
   return 1.0f / (1.0f + __expf(-v));
@@ -1238,89 +1243,44 @@ __device__ __forceinline__ bool arrive_is_last(int* __restrict__ ticket) {
 }
 
 // SGD apply + gradient zeroing over the whole bucket by ONE 256-thread
-// block (the last arriver): p += step*g; g = 0.  Same float4 split as
-// k_update: 585 vectors + a 3-float scalar tail.
+// block (the last arriver): sgd_apply4 / sgd_apply1 in the same float4 split
+// as k_update, 585 vectors + a 3-float scalar tail.  With MOM the block is
+// the only reader and writer of vel in the launch.  vel was written by the
+// last arriver of the previous launch with plain stores and has crossed a
+// kernel boundary since, exactly like params: plain loads and stores, no
+// fences beyond the ticket's.
+template <bool MOM>
 __device__ __forceinline__ void update_tail(float* __restrict__ params,
                                             float* __restrict__ grads,
-                                            float step) {
+                                            float* __restrict__ vel,
+                                            float step, const MomArgs& o) {
   constexpr int NV = N_PARAMS / 4;
-  for (int i4 = threadIdx.x; i4 < NV; i4 += 256) {
-    const int i = i4 * 4;
-    float4 pv = *reinterpret_cast<float4*>(params + i);
-    const float4 gv = *reinterpret_cast<float4*>(grads + i);
-    pv.x += step * gv.x;
-    pv.y += step * gv.y;
-    pv.z += step * gv.z;
-    pv.w += step * gv.w;
-    *reinterpret_cast<float4*>(params + i) = pv;
-    *reinterpret_cast<float4*>(grads + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
+  for (int i4 = threadIdx.x; i4 < NV; i4 += 256)
+    sgd_apply4<MOM>(params, grads, vel, i4 * 4, step, o);
   const int u = NV * 4 + threadIdx.x;
-  if (u < N_PARAMS) {
-    params[u] += step * grads[u];
-    grads[u] = 0.f;
-  }
+  if (u < N_PARAMS) sgd_apply1<MOM>(params, grads, vel, u, step, o);
 }
 
-// ---------------------------------------------------------------------------
-// Momentum / Nesterov / weight-decay form of the update, shared by the _mom
-// variant of every update site (ascent convention, g as the plain sites
-// read it):
-//   u = scale*g - wd*p;  v = mu*v + u;  p += dt*v
-//   nesterov:            p += dt*(u + mu*v)     (v the freshly updated one)
-// v is the fp32 velocity bucket, same flat layout as params.  The plain
-// kernels are separate instantiations and never see these arguments.
-// ---------------------------------------------------------------------------
-struct MomArgs {
-  float scale, dt, mu, wd;
-  int nesterov;
-};
-
-__device__ __forceinline__ float mom_apply(float p, float g, float& v,
-                                           const MomArgs& o) {
-  const float u = o.scale * g - o.wd * p;
-  v = o.mu * v + u;
-  return p + o.dt * (o.nesterov ? u + o.mu * v : v);
+// Weight gradients with the SGD update as the tail of the same launch
+// (two-launch training step).  Gradient code is wgrad_body, unchanged; the
+// block that arrives last applies the update, zeroes the bucket and resets
+// the ticket for the next launch.
+template <typename act_t, bool MOM>
+__device__ __forceinline__ void wgrad_update_body(
+    const act_t* __restrict__ x, const act_t* __restrict__ a1g,
+    const act_t* __restrict__ a2g, const float* __restrict__ dzg,
+    const float* __restrict__ dz2g, const act_t* __restrict__ dz1g,
+    float* __restrict__ grads, int B, int GC, int GS, int FS, int roles,
+    float* __restrict__ params, float step, float* __restrict__ vel,
+    const MomArgs& o, int* __restrict__ ticket) {
+  wgrad_body<act_t, true>(x, a1g, a2g, dzg, dz2g, dz1g, grads, B, GC, GS,
+                          FS, roles);
+  if (!arrive_is_last(ticket)) return;
+  update_tail<MOM>(params, grads, vel, step, o);
+  if (threadIdx.x == 0)
+    __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__device__ __forceinline__ void mom_apply4(float4& p, const float4& g,
-                                           float4& v, const MomArgs& o) {
-  p.x = mom_apply(p.x, g.x, v.x, o);
-  p.y = mom_apply(p.y, g.y, v.y, o);
-  p.z = mom_apply(p.z, g.z, v.z, o);
-  p.w = mom_apply(p.w, g.w, v.w, o);
-}
-
-// update_tail with velocity: the same 585 float4 + 3-float split.  Only
-// the last-arriving block runs this, so it is the only reader and writer of
-// vel in the launch.  vel was written by the last arriver of the previous
-// launch with plain stores and has crossed a kernel boundary since, exactly
-// like params: plain loads and stores, no fences beyond the ticket's.
-__device__ __forceinline__ void update_tail_mom(float* __restrict__ params,
-                                                float* __restrict__ grads,
-                                                float* __restrict__ vel,
-                                                const MomArgs o) {
-  constexpr int NV = N_PARAMS / 4;
-  for (int i4 = threadIdx.x; i4 < NV; i4 += 256) {
-    const int i = i4 * 4;
-    float4 pv = *reinterpret_cast<float4*>(params + i);
-    float4 vv = *reinterpret_cast<float4*>(vel + i);
-    const float4 gv = *reinterpret_cast<float4*>(grads + i);
-    mom_apply4(pv, gv, vv, o);
-    *reinterpret_cast<float4*>(params + i) = pv;
-    *reinterpret_cast<float4*>(vel + i) = vv;
-    *reinterpret_cast<float4*>(grads + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  const int u = NV * 4 + threadIdx.x;
-  if (u < N_PARAMS) {
-    float v = vel[u];
-    params[u] = mom_apply(params[u], grads[u], v, o);
-    vel[u] = v;
-    grads[u] = 0.f;
-  }
-}
-
-// k_wgrad_update (below) with the momentum tail.
 template <typename act_t>
 __global__ __launch_bounds__(256) void k_wgrad_update_mom(
     const act_t* __restrict__ x, const act_t* __restrict__ a1g,
@@ -1329,18 +1289,10 @@ __global__ __launch_bounds__(256) void k_wgrad_update_mom(
     float* __restrict__ grads, int B, int GC, int GS, int FS, int roles,
     float* __restrict__ params, float* __restrict__ vel, MomArgs o,
     int* __restrict__ ticket) {
-  wgrad_body<act_t, true>(x, a1g, a2g, dzg, dz2g, dz1g, grads, B, GC, GS,
-                          FS, roles);
-  if (!arrive_is_last(ticket)) return;
-  update_tail_mom(params, grads, vel, o);
-  if (threadIdx.x == 0)
-    __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  wgrad_update_body<act_t, true>(x, a1g, a2g, dzg, dz2g, dz1g, grads, B, GC,
+                                 GS, FS, roles, params, 0.f, vel, o, ticket);
 }
 
-// Weight gradients with the SGD update as the tail of the same launch
-// (two-launch training step).  Gradient code is wgrad_body, unchanged; the
-// block that arrives last applies the update, zeroes the bucket and resets
-// the ticket for the next launch.
 template <typename act_t>
 __global__ __launch_bounds__(256) void k_wgrad_update(
     const act_t* __restrict__ x, const act_t* __restrict__ a1g,
@@ -1348,64 +1300,42 @@ __global__ __launch_bounds__(256) void k_wgrad_update(
     const float* __restrict__ dz2g, const act_t* __restrict__ dz1g,
     float* __restrict__ grads, int B, int GC, int GS, int FS, int roles,
     float* __restrict__ params, float step, int* __restrict__ ticket) {
-  wgrad_body<act_t, true>(x, a1g, a2g, dzg, dz2g, dz1g, grads, B, GC, GS,
-                          FS, roles);
-  if (!arrive_is_last(ticket)) return;
-  update_tail(params, grads, step);
-  if (threadIdx.x == 0)
-    __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  wgrad_update_body<act_t, false>(x, a1g, a2g, dzg, dz2g, dz1g, grads, B, GC,
+                                  GS, FS, roles, params, step, nullptr,
+                                  MomArgs{}, ticket);
 }
 
 // ---------------------------------------------------------------------------
-// SGD apply + gradient zeroing:  p += dt*scale*g;  g = 0.
+// SGD apply + gradient zeroing as a launch of its own: one float4 per thread
+// across the grid (the bucket is 16B-aligned), scalar tail.
 // ---------------------------------------------------------------------------
+template <bool MOM>
+__device__ __forceinline__ void update_body(float* __restrict__ params,
+                                            float* __restrict__ grads,
+                                            float* __restrict__ vel,
+                                            float step, const MomArgs& o) {
+  const int i4 = blockIdx.x * 256 + threadIdx.x;
+  const int i = i4 * 4;
+  if (i + 3 < N_PARAMS) {
+    sgd_apply4<MOM>(params, grads, vel, i, step, o);
+  } else if (i < N_PARAMS) {
+    for (int u = i; u < N_PARAMS; ++u)
+      sgd_apply1<MOM>(params, grads, vel, u, step, o);
+  }
+}
+
 __global__ __launch_bounds__(256) void k_update(float* __restrict__ params,
                                                 float* __restrict__ grads,
                                                 float step) {
-  // float4 per thread (the bucket is 16B-aligned); scalar tail
-  const int i4 = blockIdx.x * 256 + threadIdx.x;
-  const int i = i4 * 4;
-  if (i + 3 < N_PARAMS) {
-    float4 pv = *reinterpret_cast<float4*>(params + i);
-    const float4 gv = *reinterpret_cast<float4*>(grads + i);
-    pv.x += step * gv.x;
-    pv.y += step * gv.y;
-    pv.z += step * gv.z;
-    pv.w += step * gv.w;
-    *reinterpret_cast<float4*>(params + i) = pv;
-    *reinterpret_cast<float4*>(grads + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-  } else if (i < N_PARAMS) {
-    for (int u = i; u < N_PARAMS; ++u) {
-      params[u] += step * grads[u];
-      grads[u] = 0.f;
-    }
-  }
+  update_body<false>(params, grads, nullptr, step, MomArgs{});
 }
 
-// k_update with velocity (mom_apply): same float4 body + 3-float tail, vel
-// read and written as float4 alongside params.
 __global__ __launch_bounds__(256) void k_update_mom(
     float* __restrict__ params, float* __restrict__ grads,
     float* __restrict__ vel, MomArgs o) {
-  const int i4 = blockIdx.x * 256 + threadIdx.x;
-  const int i = i4 * 4;
-  if (i + 3 < N_PARAMS) {
-    float4 pv = *reinterpret_cast<float4*>(params + i);
-    float4 vv = *reinterpret_cast<float4*>(vel + i);
-    const float4 gv = *reinterpret_cast<float4*>(grads + i);
-    mom_apply4(pv, gv, vv, o);
-    *reinterpret_cast<float4*>(params + i) = pv;
-    *reinterpret_cast<float4*>(vel + i) = vv;
-    *reinterpret_cast<float4*>(grads + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-  } else if (i < N_PARAMS) {
-    for (int u = i; u < N_PARAMS; ++u) {
-      float v = vel[u];
-      params[u] = mom_apply(params[u], grads[u], v, o);
-      vel[u] = v;
-      grads[u] = 0.f;
-    }
-  }
+  update_body<true>(params, grads, vel, 0.f, o);
 }
+
 
 // ---------------------------------------------------------------------------
 // Second kernel of the in-block weight-grad step: batch-reduce + SGD apply.
@@ -1527,8 +1457,11 @@ __global__ __launch_bounds__(256) void k_reduce_update_mom(
 }  // namespace pcnn
 
 // ---------------------------------------------------------------------------
-// extern "C" launchers (called from the pybind layer; no torch headers here).
-// All return hipError_t as int.
+// extern "C" launchers, declared in ../pcnn_launch.h (called from the pybind
+// layer and the native tools; no torch headers here).  All return hipError_t
+// as int.  A launcher that applies the update takes the optimizer as a
+// pcnn_opt: vel == NULL launches the plain kernel with opt->step, anything
+// else the _mom kernel.
 // ---------------------------------------------------------------------------
 
 using namespace pcnn;
@@ -1538,86 +1471,24 @@ template <int MODE>
 int launch_fwdbwd_mode(const void* x, const float* params, void* a1, void* a2,
                        float* y, float* dz, float* dz2, void* dz1,
                        const int* labels, float* loss_accum, int* correct,
-                       int B, int act_is_bf16, int pool_mode, int loss_mode,
+                       int B, int act, int pool_mode, int loss_mode,
                        float* grads, int wgrad_fuse, hipStream_t stream) {
   dim3 grid(B), block(256);
-  if (act_is_bf16 == 1) {
-    hipLaunchKernelGGL((k_fwdbwd<bf16, MODE>), grid, block, 0, stream,
-                       (const bf16*)x, params, (bf16*)a1, (bf16*)a2, y, dz,
-                       dz2, (bf16*)dz1, labels, loss_accum, correct, B,
-                       pool_mode, loss_mode, grads, wgrad_fuse);
-  } else if (act_is_bf16 == 2) {
-    hipLaunchKernelGGL((k_fwdbwd<fp16, MODE>), grid, block, 0, stream,
-                       (const fp16*)x, params, (fp16*)a1, (fp16*)a2, y, dz,
-                       dz2, (fp16*)dz1, labels, loss_accum, correct, B,
-                       pool_mode, loss_mode, grads, wgrad_fuse);
-  } else {
-    hipLaunchKernelGGL((k_fwdbwd<float, MODE>), grid, block, 0, stream,
-                       (const float*)x, params, (float*)a1, (float*)a2, y, dz,
-                       dz2, (float*)dz1, labels, loss_accum, correct, B,
-                       pool_mode, loss_mode, grads, wgrad_fuse);
-  }
+  PCNN_DISPATCH(act, hipLaunchKernelGGL(
+                         (k_fwdbwd<act_t, MODE>), grid, block, 0, stream,
+                         (const act_t*)x, params, (act_t*)a1, (act_t*)a2, y,
+                         dz, dz2, (act_t*)dz1, labels, loss_accum, correct, B,
+                         pool_mode, loss_mode, grads, wgrad_fuse));
   return (int)hipGetLastError();
 }
-}  // namespace
 
-extern "C" {
-
-int pcnn_launch_fwdbwd_ex2(const void* x, const float* params, void* a1,
-                           void* a2, float* y, float* dz, float* dz2,
-                           void* dz1, const int* labels, float* loss_accum,
-                           int* correct, int B, int act_is_bf16, int mode,
-                           int pool_mode, int loss_mode, float* grads,
-                           int wgrad_fuse, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  switch (mode) {
-    case MODE_TRAIN:
-      return launch_fwdbwd_mode<MODE_TRAIN>(x, params, a1, a2, y, dz, dz2,
-                                            dz1, labels, loss_accum, correct,
-                                            B, act_is_bf16, pool_mode,
-                                            loss_mode, grads, wgrad_fuse, s);
-    case MODE_EVAL:
-      return launch_fwdbwd_mode<MODE_EVAL>(x, params, a1, a2, y, dz, dz2, dz1,
-                                           labels, loss_accum, correct, B,
-                                           act_is_bf16, pool_mode, loss_mode,
-                                           grads, wgrad_fuse, s);
-    default:
-      return launch_fwdbwd_mode<MODE_INFER>(x, params, a1, a2, y, dz, dz2,
-                                            dz1, labels, loss_accum, correct,
-                                            B, act_is_bf16, pool_mode,
-                                            loss_mode, grads, wgrad_fuse, s);
-  }
-}
-
-int pcnn_launch_fwdbwd_ex(const void* x, const float* params, void* a1,
-                          void* a2, float* y, float* dz, float* dz2,
-                          void* dz1, const int* labels, float* loss_accum,
-                          int* correct, int B, int act_is_bf16, int mode,
-                          int pool_mode, int loss_mode, void* stream) {
-  return pcnn_launch_fwdbwd_ex2(x, params, a1, a2, y, dz, dz2, dz1, labels,
-                                loss_accum, correct, B, act_is_bf16, mode,
-                                pool_mode, loss_mode, nullptr, 0, stream);
-}
-
-int pcnn_launch_fwdbwd(const void* x, const float* params, void* a1, void* a2,
-                       float* y, float* dz, float* dz2, void* dz1,
-                       const int* labels, float* loss_accum, int* correct,
-                       int B, int act_is_bf16, int mode, void* stream) {
-  return pcnn_launch_fwdbwd_ex(x, params, a1, a2, y, dz, dz2, dz1, labels,
-                               loss_accum, correct, B, act_is_bf16, mode, 0,
-                               0, stream);
-}
-
-// chunk_imgs is the conv1 slices-per-channel knob (GC); <=0 -> default.
-// ticket == nullptr launches the plain k_wgrad; otherwise k_wgrad_update
-// with the same grid.
-static int launch_wgrad_any(const void* x, const void* a1, const void* a2,
-                            const float* dz, const float* dz2,
-                            const void* dz1, float* grads, int B,
-                            int act_is_bf16, int chunk_imgs, int roles,
-                            float* params, float step, int* ticket,
-                            void* stream, float* vel = nullptr,
-                            const MomArgs* mom = nullptr) {
+// ticket == nullptr launches the plain k_wgrad; otherwise k_wgrad_update or
+// k_wgrad_update_mom (by opt->vel) with the same grid.
+int launch_wgrad_any(const void* x, const void* a1, const void* a2,
+                     const float* dz, const float* dz2, const void* dz1,
+                     float* grads, int B, int act, int chunk_imgs, int roles,
+                     float* params, const pcnn_opt* opt, int* ticket,
+                     hipStream_t s) {
   // Batch-adaptive defaults: ~36 (image,position) items per conv thread,
   // pool slices at GC/4, fc batch slices of ~64 images.
   int GC = chunk_imgs > 0 ? chunk_imgs : (int)(4.0f * __builtin_cbrtf((float)B) + 0.5f);
@@ -1634,73 +1505,82 @@ static int launch_wgrad_any(const void* x, const void* a1, const void* a2,
   if (FS < 1) FS = 1;
   if (FS > 32) FS = 32;
   dim3 grid(C1_CH * GC + GS + FS * FC_BLOCKS), block(256);
+  PCNN_DISPATCH(act, {
+    const act_t *xs = (const act_t*)x, *a1s = (const act_t*)a1,
+                *a2s = (const act_t*)a2, *dz1s = (const act_t*)dz1;
+    if (ticket == nullptr)
+      hipLaunchKernelGGL((k_wgrad<act_t>), grid, block, 0, s, xs, a1s, a2s,
+                         dz, dz2, dz1s, grads, B, GC, GS, FS, roles);
+    else if (opt->vel != nullptr)
+      hipLaunchKernelGGL((k_wgrad_update_mom<act_t>), grid, block, 0, s, xs,
+                         a1s, a2s, dz, dz2, dz1s, grads, B, GC, GS, FS, roles,
+                         params, opt->vel, mom_args(opt), ticket);
+    else
+      hipLaunchKernelGGL((k_wgrad_update<act_t>), grid, block, 0, s, xs, a1s,
+                         a2s, dz, dz2, dz1s, grads, B, GC, GS, FS, roles,
+                         params, opt->step, ticket);
+  });
+  return (int)hipGetLastError();
+}
+}  // namespace
+
+extern "C" {
+
+int pcnn_launch_fwdbwd(const void* x, const float* params, void* a1, void* a2,
+                       float* y, float* dz, float* dz2, void* dz1,
+                       const int* labels, float* loss_accum, int* correct,
+                       int B, int act, int mode, int pool_mode, int loss_mode,
+                       float* grads, int wgrad_fuse, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (ticket != nullptr && mom != nullptr) {
-    if (act_is_bf16 == 1) {
-      hipLaunchKernelGGL((k_wgrad_update_mom<bf16>), grid, block, 0, s,
-                         (const bf16*)x, (const bf16*)a1, (const bf16*)a2, dz,
-                         dz2, (const bf16*)dz1, grads, B, GC, GS, FS, roles,
-                         params, vel, *mom, ticket);
-    } else if (act_is_bf16 == 2) {
-      hipLaunchKernelGGL((k_wgrad_update_mom<fp16>), grid, block, 0, s,
-                         (const fp16*)x, (const fp16*)a1, (const fp16*)a2, dz,
-                         dz2, (const fp16*)dz1, grads, B, GC, GS, FS, roles,
-                         params, vel, *mom, ticket);
-    } else {
-      hipLaunchKernelGGL((k_wgrad_update_mom<float>), grid, block, 0, s,
-                         (const float*)x, (const float*)a1, (const float*)a2,
-                         dz, dz2, (const float*)dz1, grads, B, GC, GS, FS,
-                         roles, params, vel, *mom, ticket);
-    }
-  } else if (ticket != nullptr) {
-    if (act_is_bf16 == 1) {
-      hipLaunchKernelGGL((k_wgrad_update<bf16>), grid, block, 0, s,
-                         (const bf16*)x, (const bf16*)a1, (const bf16*)a2, dz,
-                         dz2, (const bf16*)dz1, grads, B, GC, GS, FS, roles,
-                         params, step, ticket);
-    } else if (act_is_bf16 == 2) {
-      hipLaunchKernelGGL((k_wgrad_update<fp16>), grid, block, 0, s,
-                         (const fp16*)x, (const fp16*)a1, (const fp16*)a2, dz,
-                         dz2, (const fp16*)dz1, grads, B, GC, GS, FS, roles,
-                         params, step, ticket);
-    } else {
-      hipLaunchKernelGGL((k_wgrad_update<float>), grid, block, 0, s,
-                         (const float*)x, (const float*)a1, (const float*)a2,
-                         dz, dz2, (const float*)dz1, grads, B, GC, GS, FS,
-                         roles, params, step, ticket);
-    }
-  } else if (act_is_bf16 == 1) {
-    hipLaunchKernelGGL((k_wgrad<bf16>), grid, block, 0, s, (const bf16*)x,
-                       (const bf16*)a1, (const bf16*)a2, dz, dz2,
-                       (const bf16*)dz1, grads, B, GC, GS, FS, roles);
-  } else if (act_is_bf16 == 2) {
-    hipLaunchKernelGGL((k_wgrad<fp16>), grid, block, 0, s, (const fp16*)x,
-                       (const fp16*)a1, (const fp16*)a2, dz, dz2,
-                       (const fp16*)dz1, grads, B, GC, GS, FS, roles);
-  } else {
-    hipLaunchKernelGGL((k_wgrad<float>), grid, block, 0, s, (const float*)x,
-                       (const float*)a1, (const float*)a2, dz, dz2,
-                       (const float*)dz1, grads, B, GC, GS, FS, roles);
+  switch (mode) {
+    case MODE_TRAIN:
+      return launch_fwdbwd_mode<MODE_TRAIN>(x, params, a1, a2, y, dz, dz2,
+                                            dz1, labels, loss_accum, correct,
+                                            B, act, pool_mode, loss_mode,
+                                            grads, wgrad_fuse, s);
+    case MODE_EVAL:
+      return launch_fwdbwd_mode<MODE_EVAL>(x, params, a1, a2, y, dz, dz2, dz1,
+                                           labels, loss_accum, correct, B,
+                                           act, pool_mode, loss_mode, grads,
+                                           wgrad_fuse, s);
+    default:
+      return launch_fwdbwd_mode<MODE_INFER>(x, params, a1, a2, y, dz, dz2,
+                                            dz1, labels, loss_accum, correct,
+                                            B, act, pool_mode, loss_mode,
+                                            grads, wgrad_fuse, s);
   }
+}
+
+int pcnn_launch_wgrad(const void* x, const void* a1, const void* a2,
+                      const float* dz, const float* dz2, const void* dz1,
+                      float* grads, int B, int act, int chunk_imgs, int roles,
+                      void* stream) {
+  return launch_wgrad_any(x, a1, a2, dz, dz2, dz1, grads, B, act, chunk_imgs,
+                          roles, nullptr, nullptr, nullptr,
+                          (hipStream_t)stream);
+}
+
+int pcnn_launch_update(float* params, float* grads, const pcnn_opt* opt,
+                       void* stream) {
+  if (opt == nullptr) return (int)hipErrorInvalidValue;
+  dim3 grid((N_PARAMS / 4 + 255) / 256), block(256);
+  if (opt->vel != nullptr)
+    hipLaunchKernelGGL(k_update_mom, grid, block, 0, (hipStream_t)stream,
+                       params, grads, opt->vel, mom_args(opt));
+  else
+    hipLaunchKernelGGL(k_update, grid, block, 0, (hipStream_t)stream, params,
+                       grads, opt->step);
   return (int)hipGetLastError();
 }
 
-int pcnn_launch_wgrad_ex(const void* x, const void* a1, const void* a2,
-                         const float* dz, const float* dz2, const void* dz1,
-                         float* grads, int B, int act_is_bf16, int chunk_imgs,
-                         int roles, void* stream) {
-  return launch_wgrad_any(x, a1, a2, dz, dz2, dz1, grads, B, act_is_bf16,
-                          chunk_imgs, roles, nullptr, 0.f, nullptr, stream);
-}
-
-// Weight gradients + SGD update in one launch (k_wgrad_update).  `ticket`
-// is one device int32 that reads 0 before the launch and 0 again after it.
+// Weight gradients + SGD update in one launch (k_wgrad_update[_mom]).
 int pcnn_launch_wgrad_update(const void* x, const void* a1, const void* a2,
                              const float* dz, const float* dz2,
                              const void* dz1, float* grads, float* params,
-                             float step, int* ticket, int B, int act_is_bf16,
+                             const pcnn_opt* opt, int* ticket, int B, int act,
                              int chunk_imgs, int roles, void* stream) {
-  if (ticket == nullptr || params == nullptr) return (int)hipErrorInvalidValue;
+  if (ticket == nullptr || params == nullptr || opt == nullptr)
+    return (int)hipErrorInvalidValue;
   // Measured crossover (MI355X, us/step, fused vs three launches in one
   // job): B=16 17.16 vs 17.37, 64 18.45 vs 18.96, 256 23.64 vs 23.88,
   // 1024 42.31 vs 42.43, 4096 bf16 101.2 vs 100.7, 4096 fp16 101.6 vs
@@ -1708,123 +1588,87 @@ int pcnn_launch_wgrad_update(const void* x, const void* a1, const void* a2,
   // thousands of blocks that each drain and draw a ticket have used it up
   // and the difference is noise, so large batches keep the kernel boundary.
   if (B > 2048) {
-    const int err =
-        launch_wgrad_any(x, a1, a2, dz, dz2, dz1, grads, B, act_is_bf16,
-                         chunk_imgs, roles, nullptr, 0.f, nullptr, stream);
+    const int err = pcnn_launch_wgrad(x, a1, a2, dz, dz2, dz1, grads, B, act,
+                                      chunk_imgs, roles, stream);
     if (err != 0) return err;
-    dim3 ugrid((N_PARAMS / 4 + 255) / 256), ublock(256);
-    hipLaunchKernelGGL(k_update, ugrid, ublock, 0, (hipStream_t)stream,
-                       params, grads, step);
-    return (int)hipGetLastError();
+    return pcnn_launch_update(params, grads, opt, stream);
   }
-  return launch_wgrad_any(x, a1, a2, dz, dz2, dz1, grads, B, act_is_bf16,
-                          chunk_imgs, roles, params, step, ticket, stream);
+  return launch_wgrad_any(x, a1, a2, dz, dz2, dz1, grads, B, act, chunk_imgs,
+                          roles, params, opt, ticket, (hipStream_t)stream);
 }
 
-// Which kernel forms the slab: 0 = cell (k_fwdbwd<.., INBLOCK>, one lane per
-// pool cell, 256 threads), 1 = pair (k_fwdbwd_pair, two lanes per cell, 512
-// threads), -1 = the default below.
-int pcnn_inblock_default_variant() { return INBLOCK_DEFAULT_VARIANT; }
+int pcnn_inblock_default_variant(void) { return INBLOCK_DEFAULT_VARIANT; }
 
 // First kernel of the in-block weight-grad step in train mode.  Writes a2,
 // y, dz, the loss sum and rows [0, B) of gslab ([>= B][GSLAB_LD] fp32); a1,
-// dz1 and dz2 are not produced.
-int pcnn_launch_fwdbwd_inblock_v(const void* x, const float* params, void* a2,
-                                 float* y, float* dz, const int* labels,
-                                 float* loss_accum, float* gslab, int B,
-                                 int act_is_bf16, int pool_mode,
-                                 int loss_mode, int variant, void* stream) {
+// dz1 and dz2 are not produced.  variant: 0 = cell (k_fwdbwd<.., INBLOCK>,
+// one lane per pool cell, 256 threads), 1 = pair (k_fwdbwd_pair, two lanes
+// per cell, 512 threads), -1 = INBLOCK_DEFAULT_VARIANT.
+int pcnn_launch_fwdbwd_inblock(const void* x, const float* params, void* a2,
+                               float* y, float* dz, const int* labels,
+                               float* loss_accum, float* gslab, int B, int act,
+                               int pool_mode, int loss_mode, int variant,
+                               void* stream) {
   if (gslab == nullptr || dz == nullptr || B < 1 || variant < -1 ||
       variant > 1)
     return (int)hipErrorInvalidValue;
   if (variant < 0) variant = INBLOCK_DEFAULT_VARIANT;
   hipStream_t s = (hipStream_t)stream;
+  dim3 grid(B);
   if (variant == 1) {
-    dim3 grid(B), block(PR_THREADS);
-    if (act_is_bf16 == 1) {
-      hipLaunchKernelGGL((k_fwdbwd_pair<bf16>), grid, block, 0, s,
-                         (const bf16*)x, params, (bf16*)a2, y, dz, labels,
-                         loss_accum, B, pool_mode, loss_mode, gslab);
-    } else if (act_is_bf16 == 2) {
-      hipLaunchKernelGGL((k_fwdbwd_pair<fp16>), grid, block, 0, s,
-                         (const fp16*)x, params, (fp16*)a2, y, dz, labels,
-                         loss_accum, B, pool_mode, loss_mode, gslab);
-    } else {
-      hipLaunchKernelGGL((k_fwdbwd_pair<float>), grid, block, 0, s,
-                         (const float*)x, params, (float*)a2, y, dz, labels,
-                         loss_accum, B, pool_mode, loss_mode, gslab);
-    }
-    return (int)hipGetLastError();
-  }
-  dim3 grid(B), block(256);
-  if (act_is_bf16 == 1) {
-    hipLaunchKernelGGL((k_fwdbwd<bf16, MODE_TRAIN, true>), grid, block, 0, s,
-                       (const bf16*)x, params, (bf16*)nullptr, (bf16*)a2, y,
-                       dz, (float*)nullptr, (bf16*)nullptr, labels,
-                       loss_accum, (int*)nullptr, B, pool_mode, loss_mode,
-                       gslab, 0);
-  } else if (act_is_bf16 == 2) {
-    hipLaunchKernelGGL((k_fwdbwd<fp16, MODE_TRAIN, true>), grid, block, 0, s,
-                       (const fp16*)x, params, (fp16*)nullptr, (fp16*)a2, y,
-                       dz, (float*)nullptr, (fp16*)nullptr, labels,
-                       loss_accum, (int*)nullptr, B, pool_mode, loss_mode,
-                       gslab, 0);
+    PCNN_DISPATCH(act, hipLaunchKernelGGL(
+                           (k_fwdbwd_pair<act_t>), grid, dim3(PR_THREADS), 0,
+                           s, (const act_t*)x, params, (act_t*)a2, y, dz,
+                           labels, loss_accum, B, pool_mode, loss_mode,
+                           gslab));
   } else {
-    hipLaunchKernelGGL((k_fwdbwd<float, MODE_TRAIN, true>), grid, block, 0, s,
-                       (const float*)x, params, (float*)nullptr, (float*)a2,
-                       y, dz, (float*)nullptr, (float*)nullptr, labels,
-                       loss_accum, (int*)nullptr, B, pool_mode, loss_mode,
-                       gslab, 0);
+    PCNN_DISPATCH(act, hipLaunchKernelGGL(
+                           (k_fwdbwd<act_t, MODE_TRAIN, true>), grid,
+                           dim3(256), 0, s, (const act_t*)x, params,
+                           (act_t*)nullptr, (act_t*)a2, y, dz,
+                           (float*)nullptr, (act_t*)nullptr, labels,
+                           loss_accum, (int*)nullptr, B, pool_mode, loss_mode,
+                           gslab, 0));
   }
   return (int)hipGetLastError();
 }
 
-int pcnn_launch_fwdbwd_inblock(const void* x, const float* params, void* a2,
-                               float* y, float* dz, const int* labels,
-                               float* loss_accum, float* gslab, int B,
-                               int act_is_bf16, int pool_mode, int loss_mode,
-                               void* stream) {
-  return pcnn_launch_fwdbwd_inblock_v(x, params, a2, y, dz, labels,
-                                      loss_accum, gslab, B, act_is_bf16,
-                                      pool_mode, loss_mode, -1, stream);
-}
-
-// Second kernel of the in-block weight-grad step (k_reduce_update).
+// Second kernel of the in-block weight-grad step (k_reduce_update[_mom]).
 int pcnn_launch_reduce_update(const float* gslab, const void* a2,
-                              const float* dz, float* params, float step,
-                              int B, int act_is_bf16, void* stream) {
-  if (gslab == nullptr || params == nullptr || B < 1)
+                              const float* dz, float* params,
+                              const pcnn_opt* opt, int B, int act,
+                              void* stream) {
+  if (gslab == nullptr || params == nullptr || opt == nullptr || B < 1)
     return (int)hipErrorInvalidValue;
   dim3 grid(RU_BLOCKS), block(256);
   hipStream_t s = (hipStream_t)stream;
-  if (act_is_bf16 == 1) {
-    hipLaunchKernelGGL((k_reduce_update<bf16>), grid, block, 0, s, gslab,
-                       (const bf16*)a2, dz, params, step, B);
-  } else if (act_is_bf16 == 2) {
-    hipLaunchKernelGGL((k_reduce_update<fp16>), grid, block, 0, s, gslab,
-                       (const fp16*)a2, dz, params, step, B);
-  } else {
-    hipLaunchKernelGGL((k_reduce_update<float>), grid, block, 0, s, gslab,
-                       (const float*)a2, dz, params, step, B);
-  }
+  if (opt->vel != nullptr)
+    PCNN_DISPATCH(act, hipLaunchKernelGGL(
+                           (k_reduce_update_mom<act_t>), grid, block, 0, s,
+                           gslab, (const act_t*)a2, dz, params, opt->vel,
+                           mom_args(opt), B));
+  else
+    PCNN_DISPATCH(act, hipLaunchKernelGGL(
+                           (k_reduce_update<act_t>), grid, block, 0, s, gslab,
+                           (const act_t*)a2, dz, params, opt->step, B));
   return (int)hipGetLastError();
 }
 
 // Largest batch that runs the in-block weight-grad step; above it the step
 // launcher below runs k_fwdbwd + k_wgrad_update as before.
-int pcnn_inblock_max_batch() { return INBLOCK_MAX_B; }
+int pcnn_inblock_max_batch(void) { return INBLOCK_MAX_B; }
 
 // One whole single-GPU training step with in-block weight grads:
-// k_fwdbwd<INBLOCK> -> k_reduce_update.  `grads` and `ticket` are only
-// touched by the large-batch fallback and read all-zero / 0 afterwards
-// either way.
-int pcnn_launch_step_inblock_v(const void* x, float* params, void* a1,
-                               void* a2, float* y, float* dz, float* dz2,
-                               void* dz1, const int* labels,
-                               float* loss_accum, float* grads, int* ticket,
-                               float* gslab, float step, int B,
-                               int act_is_bf16, int pool_mode, int loss_mode,
-                               int chunk_imgs, int variant, void* stream) {
+// k_fwdbwd<INBLOCK> or k_fwdbwd_pair -> k_reduce_update[_mom].  `grads` and
+// `ticket` are only touched by the large-batch fallback and read all-zero /
+// 0 afterwards either way.
+int pcnn_launch_step_inblock(const void* x, float* params, void* a1, void* a2,
+                             float* y, float* dz, float* dz2, void* dz1,
+                             const int* labels, float* loss_accum,
+                             float* grads, int* ticket, float* gslab,
+                             const pcnn_opt* opt, int B, int act,
+                             int pool_mode, int loss_mode, int chunk_imgs,
+                             int variant, void* stream) {
   // k_reduce_update walks the batch with 4 lanes per parameter, so its cost
   // grows linearly with B while k_wgrad_update spreads a larger batch over
   // more blocks.  Measured (MI355X, bf16, us/step, in-block vs
@@ -1838,163 +1682,20 @@ int pcnn_launch_step_inblock_v(const void* x, float* params, void* a1,
     // Role mask as Trainer._wroles builds it: all roles, minus the pool
     // role under max pooling.  The fc-only mask (4) belongs to fuse_wgrad,
     // which excludes this step.
-    int err = pcnn_launch_fwdbwd_ex2(x, params, a1, a2, y, dz, dz2, dz1,
-                                     labels, loss_accum, nullptr, B,
-                                     act_is_bf16, MODE_TRAIN, pool_mode,
-                                     loss_mode, grads, 0, stream);
+    int err = pcnn_launch_fwdbwd(x, params, a1, a2, y, dz, dz2, dz1, labels,
+                                 loss_accum, nullptr, B, act, MODE_TRAIN,
+                                 pool_mode, loss_mode, grads, 0, stream);
     if (err != 0) return err;
     return pcnn_launch_wgrad_update(x, a1, a2, dz, dz2, dz1, grads, params,
-                                    step, ticket, B, act_is_bf16, chunk_imgs,
+                                    opt, ticket, B, act, chunk_imgs,
                                     pool_mode == 1 ? 5 : 7, stream);
   }
-  int err = pcnn_launch_fwdbwd_inblock_v(x, params, a2, y, dz, labels,
-                                         loss_accum, gslab, B, act_is_bf16,
-                                         pool_mode, loss_mode, variant,
-                                         stream);
+  int err = pcnn_launch_fwdbwd_inblock(x, params, a2, y, dz, labels,
+                                       loss_accum, gslab, B, act, pool_mode,
+                                       loss_mode, variant, stream);
   if (err != 0) return err;
-  return pcnn_launch_reduce_update(gslab, a2, dz, params, step, B,
-                                   act_is_bf16, stream);
-}
-
-int pcnn_launch_step_inblock(const void* x, float* params, void* a1, void* a2,
-                             float* y, float* dz, float* dz2, void* dz1,
-                             const int* labels, float* loss_accum,
-                             float* grads, int* ticket, float* gslab,
-                             float step, int B, int act_is_bf16,
-                             int pool_mode, int loss_mode, int chunk_imgs,
-                             void* stream) {
-  return pcnn_launch_step_inblock_v(x, params, a1, a2, y, dz, dz2, dz1,
-                                    labels, loss_accum, grads, ticket, gslab,
-                                    step, B, act_is_bf16, pool_mode,
-                                    loss_mode, chunk_imgs, -1, stream);
-}
-
-int pcnn_launch_wgrad(const void* x, const void* a1, const void* a2,
-                      const float* dz, const float* dz2, const void* dz1,
-                      float* grads, int B, int act_is_bf16, int chunk_imgs,
-                      void* stream) {
-  return pcnn_launch_wgrad_ex(x, a1, a2, dz, dz2, dz1, grads, B, act_is_bf16,
-                              chunk_imgs, 7, stream);
-}
-
-int pcnn_launch_update(float* params, float* grads, float step, void* stream) {
-  dim3 grid((N_PARAMS / 4 + 255) / 256), block(256);
-  hipLaunchKernelGGL(k_update, grid, block, 0, (hipStream_t)stream, params,
-                     grads, step);
-  return (int)hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// Momentum variants of every launcher that applies the update.  scale and
-// dt are passed apart (not pre-multiplied); vel is the fp32 velocity bucket
-// [N_PARAMS].  Batch-size hand-offs mirror the plain launchers one for one,
-// so no batch size drops the optimizer state.
-// ---------------------------------------------------------------------------
-int pcnn_launch_update_mom(float* params, float* grads, float* vel,
-                           float scale, float dt, float mu, float wd,
-                           int nesterov, void* stream) {
-  if (vel == nullptr) return (int)hipErrorInvalidValue;
-  const MomArgs o{scale, dt, mu, wd, nesterov};
-  dim3 grid((N_PARAMS / 4 + 255) / 256), block(256);
-  hipLaunchKernelGGL(k_update_mom, grid, block, 0, (hipStream_t)stream,
-                     params, grads, vel, o);
-  return (int)hipGetLastError();
-}
-
-int pcnn_launch_wgrad_update_mom(const void* x, const void* a1,
-                                 const void* a2, const float* dz,
-                                 const float* dz2, const void* dz1,
-                                 float* grads, float* params, float* vel,
-                                 float scale, float dt, float mu, float wd,
-                                 int nesterov, int* ticket, int B,
-                                 int act_is_bf16, int chunk_imgs, int roles,
-                                 void* stream) {
-  if (ticket == nullptr || params == nullptr || vel == nullptr)
-    return (int)hipErrorInvalidValue;
-  const MomArgs o{scale, dt, mu, wd, nesterov};
-  if (B > 2048) {  // same kernel boundary as pcnn_launch_wgrad_update
-    const int err =
-        launch_wgrad_any(x, a1, a2, dz, dz2, dz1, grads, B, act_is_bf16,
-                         chunk_imgs, roles, nullptr, 0.f, nullptr, stream);
-    if (err != 0) return err;
-    return pcnn_launch_update_mom(params, grads, vel, scale, dt, mu, wd,
-                                  nesterov, stream);
-  }
-  return launch_wgrad_any(x, a1, a2, dz, dz2, dz1, grads, B, act_is_bf16,
-                          chunk_imgs, roles, params, 0.f, ticket, stream, vel,
-                          &o);
-}
-
-int pcnn_launch_reduce_update_mom(const float* gslab, const void* a2,
-                                  const float* dz, float* params, float* vel,
-                                  float scale, float dt, float mu, float wd,
-                                  int nesterov, int B, int act_is_bf16,
-                                  void* stream) {
-  if (gslab == nullptr || params == nullptr || vel == nullptr || B < 1)
-    return (int)hipErrorInvalidValue;
-  const MomArgs o{scale, dt, mu, wd, nesterov};
-  dim3 grid(RU_BLOCKS), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  if (act_is_bf16 == 1) {
-    hipLaunchKernelGGL((k_reduce_update_mom<bf16>), grid, block, 0, s, gslab,
-                       (const bf16*)a2, dz, params, vel, o, B);
-  } else if (act_is_bf16 == 2) {
-    hipLaunchKernelGGL((k_reduce_update_mom<fp16>), grid, block, 0, s, gslab,
-                       (const fp16*)a2, dz, params, vel, o, B);
-  } else {
-    hipLaunchKernelGGL((k_reduce_update_mom<float>), grid, block, 0, s, gslab,
-                       (const float*)a2, dz, params, vel, o, B);
-  }
-  return (int)hipGetLastError();
-}
-
-// pcnn_launch_step_inblock with the momentum update; the B > INBLOCK_MAX_B
-// hand-off goes to k_wgrad_update_mom with the same optimizer arguments.
-int pcnn_launch_step_inblock_mom_v(const void* x, float* params, float* vel,
-                                   void* a1, void* a2, float* y, float* dz,
-                                   float* dz2, void* dz1, const int* labels,
-                                   float* loss_accum, float* grads,
-                                   int* ticket, float* gslab, float scale,
-                                   float dt, float mu, float wd, int nesterov,
-                                   int B, int act_is_bf16, int pool_mode,
-                                   int loss_mode, int chunk_imgs, int variant,
-                                   void* stream) {
-  if (B > INBLOCK_MAX_B) {
-    int err = pcnn_launch_fwdbwd_ex2(x, params, a1, a2, y, dz, dz2, dz1,
-                                     labels, loss_accum, nullptr, B,
-                                     act_is_bf16, MODE_TRAIN, pool_mode,
-                                     loss_mode, grads, 0, stream);
-    if (err != 0) return err;
-    return pcnn_launch_wgrad_update_mom(x, a1, a2, dz, dz2, dz1, grads,
-                                        params, vel, scale, dt, mu, wd,
-                                        nesterov, ticket, B, act_is_bf16,
-                                        chunk_imgs, pool_mode == 1 ? 5 : 7,
-                                        stream);
-  }
-  int err = pcnn_launch_fwdbwd_inblock_v(x, params, a2, y, dz, labels,
-                                         loss_accum, gslab, B, act_is_bf16,
-                                         pool_mode, loss_mode, variant,
-                                         stream);
-  if (err != 0) return err;
-  return pcnn_launch_reduce_update_mom(gslab, a2, dz, params, vel, scale, dt,
-                                       mu, wd, nesterov, B, act_is_bf16,
-                                       stream);
-}
-
-int pcnn_launch_step_inblock_mom(const void* x, float* params, float* vel,
-                                 void* a1, void* a2, float* y, float* dz,
-                                 float* dz2, void* dz1, const int* labels,
-                                 float* loss_accum, float* grads, int* ticket,
-                                 float* gslab, float scale, float dt,
-                                 float mu, float wd, int nesterov, int B,
-                                 int act_is_bf16, int pool_mode,
-                                 int loss_mode, int chunk_imgs,
-                                 void* stream) {
-  return pcnn_launch_step_inblock_mom_v(x, params, vel, a1, a2, y, dz, dz2,
-                                        dz1, labels, loss_accum, grads,
-                                        ticket, gslab, scale, dt, mu, wd,
-                                        nesterov, B, act_is_bf16, pool_mode,
-                                        loss_mode, chunk_imgs, -1, stream);
+  return pcnn_launch_reduce_update(gslab, a2, dz, params, opt, B, act,
+                                   stream);
 }
 
 #ifdef PCNN_LENET_STAMPS

@@ -6,6 +6,7 @@ CPU reference ops.  Build with:
 
     python setup.py build_ext --inplace
 """
+import glob
 import os
 import subprocess
 import sys
@@ -24,19 +25,25 @@ HIP_SOURCES = [
 ]
 
 
+# Every header under csrc/: the launcher surface (pcnn_launch.h), the
+# dimensions and the shared device headers.  An edit to any of them makes
+# the HIP objects, the native CLI and the extension stale.
+HEADERS = sorted(glob.glob(os.path.join(HERE, "csrc", "**", "*.h"),
+                           recursive=True))
+
 FORCE = os.environ.get("PCNN_FORCE_REBUILD") == "1"
+
+
+def older_than(out, deps):
+    return (not os.path.exists(out)
+            or any(os.path.getmtime(out) < os.path.getmtime(d) for d in deps))
 
 
 def compile_hip_objects():
     objs = []
     for src in HIP_SOURCES:
         obj = os.path.splitext(src)[0] + ".o"
-        stale = (FORCE
-                 or not os.path.exists(obj)
-                 or os.path.getmtime(obj) < os.path.getmtime(src)
-                 or os.path.getmtime(obj) < os.path.getmtime(
-                     os.path.join(HERE, "csrc", "lenet_dims.h")))
-        if stale:
+        if FORCE or older_than(obj, [src] + HEADERS):
             cmd = [
                 os.path.join(ROCM, "bin", "hipcc"),
                 f"--offload-arch={ARCH}",
@@ -61,12 +68,7 @@ def build_native_cli(hip_objs):
     src = os.path.join(HERE, "tools", "pcnn_train.cpp")
     out = os.path.join(HERE, "tools", "pcnn_train")
     try:
-        stale = (FORCE
-                 or not os.path.exists(out)
-                 or os.path.getmtime(out) < os.path.getmtime(src)
-                 or any(os.path.getmtime(out) < os.path.getmtime(o)
-                        for o in hip_objs))
-        if stale:
+        if FORCE or older_than(out, [src] + HEADERS + hip_objs):
             obj = os.path.join(HERE, "tools", "pcnn_train.o")
             hipcc = os.path.join(ROCM, "bin", "hipcc")
             for cmd in ([hipcc, f"--offload-arch={ARCH}", "-O3",
@@ -86,6 +88,7 @@ build_native_cli(_hip_objs)
 ext = CppExtension(
     name="parallel_cnn_amd._C",
     sources=["csrc/bindings.cpp", "csrc/cpu_ops.cpp"],
+    depends=HEADERS,
     extra_objects=_hip_objs,
     libraries=["amdhip64"],
     library_dirs=[os.path.join(ROCM, "lib")],

@@ -55,17 +55,29 @@ dz1 = dmalloc(B * 3456 * 2)
 labels = dmalloc(B * 4)
 loss = dmalloc(4)
 
+class PcnnOpt(ctypes.Structure):
+    """pcnn_opt of csrc/pcnn_launch.h; vel = NULL selects plain SGD."""
+    _fields_ = [("step", ctypes.c_float), ("scale", ctypes.c_float),
+                ("dt", ctypes.c_float), ("mu", ctypes.c_float),
+                ("wd", ctypes.c_float), ("nesterov", ctypes.c_int),
+                ("vel", ctypes.c_void_p)]
+
+
+# argtypes follow the declarations in csrc/pcnn_launch.h one for one
+VP, CI = ctypes.c_void_p, ctypes.c_int
 fwd = lib.pcnn_launch_fwdbwd
+fwd.argtypes = [VP] * 11 + [CI] * 5 + [VP, CI, VP]
 wgr = lib.pcnn_launch_wgrad
+wgr.argtypes = [VP] * 7 + [CI] * 4 + [VP]
 upd = lib.pcnn_launch_update
-NULLS = ctypes.c_void_p(0)
+upd.argtypes = [VP, VP, ctypes.POINTER(PcnnOpt), VP]
+opt = PcnnOpt(step=0.001)
 
 def step():
-    hipcheck(fwd(x, params, a1, a2, y, dz, dz2, dz1, labels, loss, NULLS,
-                 B, 1, 0, NULLS))
-    hipcheck(wgr(x, a1, a2, dz, dz2, dz1, grads, B, 1, 0, NULLS))
-    upd.restype = ctypes.c_int
-    hipcheck(upd(params, grads, ctypes.c_float(0.001), NULLS))
+    hipcheck(fwd(x, params, a1, a2, y, dz, dz2, dz1, labels, loss, None,
+                 B, 1, 0, 0, 0, None, 0, None))
+    hipcheck(wgr(x, a1, a2, dz, dz2, dz1, grads, B, 1, 0, 7, None))
+    hipcheck(upd(params, grads, ctypes.byref(opt), None))
 
 for n in (200, 2000):
     t0 = time.perf_counter()

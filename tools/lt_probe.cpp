@@ -22,12 +22,7 @@
 #include <cstdlib>
 #include <vector>
 
-extern "C" int pcnn_deep_gemm_ex4(
-    const void* A, const float* Bsrc, const void* Bpre, const float* bias,
-    void* C, long long M, int K, int N, int ldA, int ldC, int b_kxn,
-    int epilogue, const void* imx, int XH, int XW, int XC, int XK, int XP,
-    const void* epi, const float* pw, void* pout, int PK, float* c32,
-    long long c32_cap, int actf, void* stream);
+#include "../csrc/pcnn_launch.h"
 
 #define CK(x)                                                      \
   do {                                                             \
@@ -129,9 +124,9 @@ int main() {
       };
       double t_lt = bench(lt);
       auto ours = [&]() {
-        pcnn_deep_gemm_ex4(A, Bf, Bb, nullptr, C, M, K, N, K, N, 1, 0,
-                           nullptr, 0, 0, 0, 0, 0, nullptr, nullptr,
-                           nullptr, 0, c32, 8 * M * N, 1, nullptr);
+        pcnn_deep_gemm(A, Bf, Bb, nullptr, C, M, K, N, K, N, 1, 0,
+                       nullptr, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, 0,
+                       c32, 8 * M * N, 1, nullptr);
       };
       double t_ours = bench(ours);
       // interleave a second round (process-variance guard)

@@ -29,21 +29,9 @@
 #include <vector>
 
 #include "../csrc/lenet_dims.h"
+#include "../csrc/pcnn_launch.h"
 
 using namespace pcnn;
-
-extern "C" {
-int pcnn_launch_fwdbwd(const void* x, const float* params, void* a1, void* a2,
-                       float* y, float* dz, float* dz2, float* dz1,
-                       const int* labels, float* loss_accum, int* correct,
-                       int B, int act_is_bf16, int mode, void* stream);
-int pcnn_launch_wgrad(const void* x, const void* a1, const void* a2,
-                      const float* dz, const float* dz2, const float* dz1,
-                      float* grads, int B, int act_is_bf16, int chunk_imgs,
-                      void* stream);
-int pcnn_launch_update(float* params, float* grads, float step, void* stream);
-const char* pcnn_hip_error_string(int err);
-}
 
 #define CHECK(x)                                                        \
   do {                                                                  \
@@ -233,6 +221,8 @@ int main(int argc, char** argv) {
   CHECK(hipMemset(d_loss, 0, 4));
 
   const float scale = a.reduction == "sum" ? 1.0f : 1.0f / (float)B;
+  pcnn_opt opt = {};  // plain SGD: no velocity
+  opt.step = a.dt * scale;
   printf("Learning\n");
   int epochs_done = 0;
   auto t0 = std::chrono::steady_clock::now();
@@ -241,11 +231,11 @@ int main(int argc, char** argv) {
       const void* xb = (const char*)d_xtr + (size_t)s * IN_PIX * 2;
       const int* yb = d_ytr + s;
       CHECK(pcnn_launch_fwdbwd(xb, d_params, d_a1, d_a2, d_y, d_dz, d_dz2,
-                               d_dz1, yb, d_loss, d_correct, B, 1, 0,
-                               nullptr));
+                               d_dz1, yb, d_loss, d_correct, B, 1, 0, 0, 0,
+                               nullptr, 0, nullptr));
       CHECK(pcnn_launch_wgrad(xb, d_a1, d_a2, d_dz, d_dz2, d_dz1, d_grads, B,
-                              1, 0, nullptr));
-      CHECK(pcnn_launch_update(d_params, d_grads, a.dt * scale, nullptr));
+                              1, 0, 7, nullptr));
+      CHECK(pcnn_launch_update(d_params, d_grads, &opt, nullptr));
     }
     float loss_sum = 0.f;
     CHECK(hipMemcpy(&loss_sum, d_loss, 4, hipMemcpyDeviceToHost));
@@ -280,7 +270,8 @@ int main(int argc, char** argv) {
     const int n = std::min(B, a.test_count - s);
     CHECK(pcnn_launch_fwdbwd((const char*)d_xte + (size_t)s * IN_PIX * 2,
                              d_params, d_a1, d_a2, d_y, d_dz, d_dz2, d_dz1,
-                             d_yte + s, d_loss, d_correct, n, 1, 1, nullptr));
+                             d_yte + s, d_loss, d_correct, n, 1, 1, 0, 0,
+                             nullptr, 0, nullptr));
   }
   int correct = 0;
   CHECK(hipMemcpy(&correct, d_correct, 4, hipMemcpyDeviceToHost));

@@ -78,7 +78,7 @@ def main():
     lib = ctypes.CDLL(LIB)
     vp, ci = ctypes.c_void_p, ctypes.c_int
     lib.pcnn_stamp_set_buffer.argtypes = [vp, ci]
-    lib.pcnn_launch_fwdbwd_inblock_v.argtypes = [vp] * 8 + [ci] * 5 + [vp]
+    lib.pcnn_launch_fwdbwd_inblock.argtypes = [vp] * 8 + [ci] * 5 + [vp]
     dev = "cuda:0"
     B = a.batch
     ad = {"bf16": torch.bfloat16, "fp16": torch.float16,
@@ -101,7 +101,7 @@ def main():
     out = {"batch": B, "dtype": a.dtype, "points": NAMES}
     for name, variant, threads in (("cell", 0, 256), ("pair", 1, 512)):
         def launch():
-            e = lib.pcnn_launch_fwdbwd_inblock_v(
+            e = lib.pcnn_launch_fwdbwd_inblock(
                 x.data_ptr(), params.data_ptr(), a2.data_ptr(), y.data_ptr(),
                 dz.data_ptr(), labels.data_ptr(), loss.data_ptr(),
                 slab.data_ptr(), B, flag, 0, 0, variant, None)
