@@ -9,6 +9,8 @@
 
 #include <torch/extension.h>
 
+#include <cmath>
+
 #include "lenet_dims.h"
 #include "pcnn_launch.h"
 
@@ -23,6 +25,9 @@ void cpu_update(at::Tensor params, at::Tensor grads, double dt, double scale);
 void cpu_update_momentum(at::Tensor params, at::Tensor grads, at::Tensor vel,
                          double dt, double scale, double mu, double wd,
                          bool nesterov);
+void cpu_update_adam(at::Tensor params, at::Tensor grads, at::Tensor m,
+                     at::Tensor sq, double dt, double scale, double beta1,
+                     double beta2, double eps, double wd, int64_t t);
 }  // namespace pcnn
 
 namespace {
@@ -108,10 +113,20 @@ float* vel_ptr(const at::Tensor& vel, const at::Tensor& params) {
   return vel.data_ptr<float>();
 }
 
+// Second-moment bucket of the Adam update.
+float* sq_ptr(const at::Tensor& sq, const at::Tensor& params) {
+  TORCH_CHECK(sq.is_cuda() && sq.scalar_type() == at::kFloat &&
+                  sq.is_contiguous() && sq.numel() == params.numel(),
+              "sq must be a contiguous device fp32 tensor with the same "
+              "numel as params");
+  return sq.data_ptr<float>();
+}
+
 // The optimizer of a launch (pcnn_opt, pcnn_launch.h): the plain bindings
 // pass the pre-multiplied step and no velocity, which selects the plain
 // kernels; the _momentum bindings pass dt and scale apart and the velocity
-// bucket.
+// bucket; the _adam bindings pass both moment buckets and the 1-based update
+// count t, from which the bias corrections are formed here in double.
 pcnn_opt plain_opt(double step) {
   return pcnn_opt{(float)step, 0.f, 0.f, 0.f, 0.f, 0, nullptr};
 }
@@ -121,6 +136,28 @@ pcnn_opt momentum_opt(const at::Tensor& vel, const at::Tensor& params,
                       bool nesterov) {
   return pcnn_opt{0.f,       (float)scale,     (float)dt,           (float)mu,
                   (float)wd, nesterov ? 1 : 0, vel_ptr(vel, params)};
+}
+
+pcnn_opt adam_opt(const at::Tensor& m, const at::Tensor& sq,
+                  const at::Tensor& params, double dt, double scale,
+                  double beta1, double beta2, double eps, double wd,
+                  int64_t t) {
+  TORCH_CHECK(t >= 1, "t is the 1-based update count");
+  pcnn_opt o = {};
+  o.scale = (float)scale;
+  o.dt = (float)dt;
+  o.mu = (float)beta1;
+  o.wd = (float)wd;
+  o.vel = vel_ptr(m, params);
+  o.kind = 1;
+  o.sq = sq_ptr(sq, params);
+  o.beta2 = (float)beta2;
+  o.eps = (float)eps;
+  o.c1 = (float)(1.0 / (1.0 - std::pow(beta1, (double)t)));
+  o.c2 = (float)(1.0 / std::sqrt(1.0 - std::pow(beta2, (double)t)));
+  o.omb1 = (float)(1.0 - beta1);
+  o.omb2 = (float)(1.0 - beta2);
+  return o;
 }
 
 void check_flat_buckets(const at::Tensor& params, const at::Tensor& grads) {
@@ -147,6 +184,19 @@ void hip_update_momentum(at::Tensor params, at::Tensor grads, at::Tensor vel,
   check_hip(pcnn_launch_update(params.data_ptr<float>(),
                                grads.data_ptr<float>(), &opt, (void*)stream),
             "update_momentum");
+}
+
+// hip_update with the Adam rule (k_update_adam).
+void hip_update_adam(at::Tensor params, at::Tensor grads, at::Tensor m,
+                     at::Tensor sq, double dt, double scale, double beta1,
+                     double beta2, double eps, double wd, int64_t t,
+                     int64_t stream) {
+  check_flat_buckets(params, grads);
+  const pcnn_opt opt =
+      adam_opt(m, sq, params, dt, scale, beta1, beta2, eps, wd, t);
+  check_hip(pcnn_launch_update(params.data_ptr<float>(),
+                               grads.data_ptr<float>(), &opt, (void*)stream),
+            "update_adam");
 }
 
 // Weight gradients with the SGD update as the tail of the same launch:
@@ -195,6 +245,21 @@ void hip_wgrad_update_momentum(at::Tensor x, at::Tensor a1, at::Tensor a2,
                     "wgrad_update_momentum");
 }
 
+// hip_wgrad_update with the Adam tail (k_wgrad_update_adam).
+void hip_wgrad_update_adam(at::Tensor x, at::Tensor a1, at::Tensor a2,
+                           at::Tensor dz, at::Tensor dz2, at::Tensor dz1,
+                           at::Tensor grads, at::Tensor params, at::Tensor m,
+                           at::Tensor sq, double dt, double scale,
+                           double beta1, double beta2, double eps, double wd,
+                           int64_t t, at::Tensor ticket, int64_t B,
+                           int64_t chunk_imgs, int64_t roles,
+                           int64_t stream) {
+  wgrad_update_impl(
+      x, a1, a2, dz, dz2, dz1, grads, params,
+      adam_opt(m, sq, params, dt, scale, beta1, beta2, eps, wd, t), ticket, B,
+      chunk_imgs, roles, stream, "wgrad_update_adam");
+}
+
 float* gslab_ptr(const at::Tensor& gslab, int64_t B) {
   TORCH_CHECK(gslab.is_cuda() && gslab.scalar_type() == at::kFloat &&
                   gslab.is_contiguous() &&
@@ -239,9 +304,9 @@ void hip_fwdbwd_inblock(at::Tensor x, at::Tensor params, at::Tensor a2,
 }
 
 // One whole training step with in-block weight grads (k_fwdbwd<INBLOCK> or
-// k_fwdbwd_pair -> k_reduce_update[_mom]); above _C.INBLOCK_MAX_BATCH the
-// launcher runs k_fwdbwd -> k_wgrad_update[_mom] instead, which is why it
-// takes every buffer.
+// k_fwdbwd_pair -> k_reduce_update[_mom|_adam]); above
+// _C.INBLOCK_MAX_BATCH the launcher runs k_fwdbwd ->
+// k_wgrad_update[_mom|_adam] instead, which is why it takes every buffer.
 void step_inblock_impl(const at::Tensor& x, const at::Tensor& params,
                        const at::Tensor& a1, const at::Tensor& a2,
                        const at::Tensor& y, const at::Tensor& dz,
@@ -311,26 +376,63 @@ void hip_step_inblock_momentum(at::Tensor x, at::Tensor params,
                     "step_inblock_momentum");
 }
 
-// Second kernel of the in-block step on its own, momentum form
-// (k_reduce_update_mom): slab rows [0, B), a2 and dz in, params and vel
-// updated.
-void hip_reduce_update_momentum(at::Tensor gslab, at::Tensor a2,
-                                at::Tensor dz, at::Tensor params,
-                                at::Tensor vel, double dt, double scale,
-                                double mu, double wd, bool nesterov,
-                                int64_t B, int64_t stream) {
+void hip_step_inblock_adam(at::Tensor x, at::Tensor params, at::Tensor m,
+                           at::Tensor sq, at::Tensor a1, at::Tensor a2,
+                           at::Tensor y, at::Tensor dz, at::Tensor dz2,
+                           at::Tensor dz1, at::Tensor labels,
+                           at::Tensor loss_accum, at::Tensor grads,
+                           at::Tensor ticket, at::Tensor gslab, double dt,
+                           double scale, double beta1, double beta2,
+                           double eps, double wd, int64_t t, int64_t B,
+                           int64_t chunk_imgs, int64_t stream,
+                           int64_t pool_mode, int64_t loss_mode,
+                           int64_t variant) {
+  step_inblock_impl(
+      x, params, a1, a2, y, dz, dz2, dz1, labels, loss_accum, grads, ticket,
+      gslab, adam_opt(m, sq, params, dt, scale, beta1, beta2, eps, wd, t), B,
+      chunk_imgs, stream, pool_mode, loss_mode, variant, "step_inblock_adam");
+}
+
+// Second kernel of the in-block step on its own: slab rows [0, B), a2 and dz
+// in, params and the optimizer state updated.
+void reduce_update_impl(const at::Tensor& gslab, const at::Tensor& a2,
+                        const at::Tensor& dz, const at::Tensor& params,
+                        const pcnn_opt& opt, int64_t B, int64_t stream,
+                        const char* what) {
   TORCH_CHECK(params.is_cuda() && params.numel() == pcnn::N_PARAMS,
               "params must be the flat device bucket");
   TORCH_CHECK(B >= 1 && a2.is_cuda() && a2.numel() >= B * pcnn::S1_OUT &&
                   dz.is_cuda() && dz.scalar_type() == at::kFloat &&
                   dz.numel() >= B * pcnn::FC_OUT,
               "buffers too small for B");
-  const pcnn_opt opt = momentum_opt(vel, params, dt, scale, mu, wd, nesterov);
   check_hip(pcnn_launch_reduce_update(gslab_ptr(gslab, B), a2.data_ptr(),
                                       dz.data_ptr<float>(),
                                       params.data_ptr<float>(), &opt, (int)B,
                                       act_flag(a2), (void*)stream),
-            "reduce_update_momentum");
+            what);
+}
+
+// Momentum form (k_reduce_update_mom).
+void hip_reduce_update_momentum(at::Tensor gslab, at::Tensor a2,
+                                at::Tensor dz, at::Tensor params,
+                                at::Tensor vel, double dt, double scale,
+                                double mu, double wd, bool nesterov,
+                                int64_t B, int64_t stream) {
+  reduce_update_impl(gslab, a2, dz, params,
+                     momentum_opt(vel, params, dt, scale, mu, wd, nesterov),
+                     B, stream, "reduce_update_momentum");
+}
+
+// Adam form (k_reduce_update_adam).
+void hip_reduce_update_adam(at::Tensor gslab, at::Tensor a2, at::Tensor dz,
+                            at::Tensor params, at::Tensor m, at::Tensor sq,
+                            double dt, double scale, double beta1,
+                            double beta2, double eps, double wd, int64_t t,
+                            int64_t B, int64_t stream) {
+  reduce_update_impl(
+      gslab, a2, dz, params,
+      adam_opt(m, sq, params, dt, scale, beta1, beta2, eps, wd, t), B, stream,
+      "reduce_update_adam");
 }
 
 // Single-GPU fused training loop: enqueues `steps` full training steps
@@ -351,13 +453,20 @@ void hip_train_steps(at::Tensor x_pool, at::Tensor labels_pool,
                      int64_t step_mode, at::Tensor ticket,
                      at::Tensor gslab, at::Tensor vel, double dt,
                      double scale, double mu, double wd, bool nesterov,
-                     int64_t variant) {
+                     int64_t variant, at::Tensor sq, double beta2, double eps,
+                     int64_t t0) {
   const int var = inblock_variant(variant);
   // a non-empty vel selects the momentum update in every step mode; dt and
-  // scale then replace the pre-multiplied step_scale
-  const pcnn_opt opt =
-      vel.numel() ? momentum_opt(vel, params, dt, scale, mu, wd, nesterov)
-                  : plain_opt(step_scale);
+  // scale then replace the pre-multiplied step_scale.  A non-empty sq
+  // selects Adam instead: vel is then m, mu is beta1, t0 is the number of
+  // updates already applied, and the bias corrections are formed again for
+  // t = t0 + st + 1 at every step of the loop below.
+  const bool adam = sq.numel() != 0;
+  TORCH_CHECK(!adam || t0 >= 0, "t0 is the number of updates applied so far");
+  pcnn_opt opt =
+      adam ? adam_opt(vel, sq, params, dt, scale, mu, beta2, eps, wd, t0 + 1)
+      : vel.numel() ? momentum_opt(vel, params, dt, scale, mu, wd, nesterov)
+                    : plain_opt(step_scale);
   TORCH_CHECK(step_mode == 3 || step_mode == 2 || step_mode == 4,
               "step_mode must be 3, 2 or 4");
   TORCH_CHECK(step_mode == 3 || !wgrad_fuse,
@@ -384,6 +493,9 @@ void hip_train_steps(at::Tensor x_pool, at::Tensor labels_pool,
     const int64_t i = st % P;
     const void* xb = xp + (size_t)i * B * pcnn::IN_PIX * esz;
     const int* lb = lp + i * B;
+    if (adam && st > 0)
+      opt = adam_opt(vel, sq, params, dt, scale, mu, beta2, eps, wd,
+                     t0 + st + 1);
     if (step_mode == 4) {
       check_hip(pcnn_launch_step_inblock(
                     xb, pp, a1.data_ptr(), a2.data_ptr(), y.data_ptr<float>(),
@@ -549,6 +661,31 @@ void deep_update_cast_momentum(at::Tensor params, at::Tensor grads,
                                   &opt, wbuf.data_ptr(), &cd.d,
                                   (void*)stream),
             "deep_update_cast_momentum");
+}
+
+// deep_update_cast with the Adam update (k_update_cast_all_adam): the bf16
+// images are cast from the post-Adam value.
+void deep_update_cast_adam(at::Tensor params, at::Tensor grads, at::Tensor m,
+                           at::Tensor sq, double dt, double scale,
+                           double beta1, double beta2, double eps, double wd,
+                           int64_t t, at::Tensor wbuf, std::vector<int64_t> R,
+                           std::vector<int64_t> C, std::vector<int64_t> K,
+                           std::vector<int64_t> Cin,
+                           std::vector<int64_t> w_off,
+                           std::vector<int64_t> bf_off,
+                           std::vector<int64_t> bfT_off,
+                           std::vector<int64_t> rot_off,
+                           std::vector<int64_t> p8_off, int64_t stream) {
+  const CastDesc cd("deep_update_cast_adam", R, C, K, Cin, w_off, bf_off,
+                    bfT_off, rot_off, p8_off);
+  TORCH_CHECK(grads.numel() == params.numel(), "grads/params size mismatch");
+  const pcnn_opt opt =
+      adam_opt(m, sq, params, dt, scale, beta1, beta2, eps, wd, t);
+  check_hip(pcnn_deep_update_cast(params.data_ptr<float>(),
+                                  grads.data_ptr<float>(), params.numel(),
+                                  &opt, wbuf.data_ptr(), &cd.d,
+                                  (void*)stream),
+            "deep_update_cast_adam");
 }
 
 void deep_wgrad_multi(std::vector<at::Tensor> a,
@@ -744,6 +881,19 @@ void deep_update_momentum(at::Tensor params, at::Tensor grads,
             "deep_update_momentum");
 }
 
+void deep_update_adam(at::Tensor params, at::Tensor grads, at::Tensor m,
+                      at::Tensor sq, double dt, double scale, double beta1,
+                      double beta2, double eps, double wd, int64_t t,
+                      int64_t stream) {
+  TORCH_CHECK(grads.numel() == params.numel(), "grads/params size mismatch");
+  const pcnn_opt opt =
+      adam_opt(m, sq, params, dt, scale, beta1, beta2, eps, wd, t);
+  check_hip(pcnn_deep_update(params.data_ptr<float>(),
+                             grads.data_ptr<float>(), params.numel(), &opt,
+                             (void*)stream),
+            "deep_update_adam");
+}
+
 void deep_mfma_selftest(at::Tensor A, at::Tensor Bm, at::Tensor D,
                         int64_t stream) {
   check_hip(pcnn_deep_mfma_selftest(A.data_ptr<float>(),
@@ -768,6 +918,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cpu_update_momentum", &pcnn::cpu_update_momentum, py::arg("params"),
         py::arg("grads"), py::arg("vel"), py::arg("dt"), py::arg("scale"),
         py::arg("mu"), py::arg("wd"), py::arg("nesterov"));
+  m.def("cpu_update_adam", &pcnn::cpu_update_adam, py::arg("params"),
+        py::arg("grads"), py::arg("m"), py::arg("sq"), py::arg("dt"),
+        py::arg("scale"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+        py::arg("wd"), py::arg("t"));
   m.def("hip_fwdbwd", &hip_fwdbwd, py::arg("x"), py::arg("params"),
         py::arg("a1"), py::arg("a2"), py::arg("y"), py::arg("dz"),
         py::arg("dz2"), py::arg("dz1"), py::arg("labels"),
@@ -789,7 +943,33 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("gslab") = at::empty({0}), py::arg("vel") = at::empty({0}),
         py::arg("dt") = 0.0, py::arg("scale") = 1.0, py::arg("mu") = 0.0,
         py::arg("wd") = 0.0, py::arg("nesterov") = false,
-        py::arg("variant") = -1);
+        py::arg("variant") = -1, py::arg("sq") = at::empty({0}),
+        py::arg("beta2") = 0.999, py::arg("eps") = 1e-8, py::arg("t0") = 0);
+  m.def("hip_update_adam", &hip_update_adam, py::arg("params"),
+        py::arg("grads"), py::arg("m"), py::arg("sq"), py::arg("dt"),
+        py::arg("scale"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+        py::arg("wd"), py::arg("t"), py::arg("stream"));
+  m.def("hip_wgrad_update_adam", &hip_wgrad_update_adam, py::arg("x"),
+        py::arg("a1"), py::arg("a2"), py::arg("dz"), py::arg("dz2"),
+        py::arg("dz1"), py::arg("grads"), py::arg("params"), py::arg("m"),
+        py::arg("sq"), py::arg("dt"), py::arg("scale"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("wd"), py::arg("t"),
+        py::arg("ticket"), py::arg("B"), py::arg("chunk_imgs"),
+        py::arg("roles"), py::arg("stream"));
+  m.def("hip_reduce_update_adam", &hip_reduce_update_adam, py::arg("gslab"),
+        py::arg("a2"), py::arg("dz"), py::arg("params"), py::arg("m"),
+        py::arg("sq"), py::arg("dt"), py::arg("scale"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("wd"), py::arg("t"),
+        py::arg("B"), py::arg("stream"));
+  m.def("hip_step_inblock_adam", &hip_step_inblock_adam, py::arg("x"),
+        py::arg("params"), py::arg("m"), py::arg("sq"), py::arg("a1"),
+        py::arg("a2"), py::arg("y"), py::arg("dz"), py::arg("dz2"),
+        py::arg("dz1"), py::arg("labels"), py::arg("loss_accum"),
+        py::arg("grads"), py::arg("ticket"), py::arg("gslab"), py::arg("dt"),
+        py::arg("scale"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+        py::arg("wd"), py::arg("t"), py::arg("B"), py::arg("chunk_imgs"),
+        py::arg("stream"), py::arg("pool_mode") = 0,
+        py::arg("loss_mode") = 0, py::arg("variant") = -1);
   m.def("hip_update_momentum", &hip_update_momentum, py::arg("params"),
         py::arg("grads"), py::arg("vel"), py::arg("dt"), py::arg("scale"),
         py::arg("mu"), py::arg("wd"), py::arg("nesterov"),
@@ -870,6 +1050,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("deep_update", &deep_update);
   m.def("deep_update_momentum", &deep_update_momentum);
   m.def("deep_update_cast_momentum", &deep_update_cast_momentum);
+  m.def("deep_update_adam", &deep_update_adam);
+  m.def("deep_update_cast_adam", &deep_update_cast_adam);
   m.def("deep_mfma_selftest", &deep_mfma_selftest);
   m.attr("N_PARAMS") = pcnn::N_PARAMS;
   m.attr("GSLAB_LD") = pcnn::GSLAB_LD;

@@ -337,4 +337,38 @@ void cpu_update_momentum(at::Tensor params, at::Tensor grads, at::Tensor vel,
   }
 }
 
+// Adam with decoupled weight decay, ascent convention (any flat size), for
+// the 1-based update count t:
+//   u = scale*g;  m = beta1*m + (1-beta1)*u;  s = beta2*s + (1-beta2)*u*u
+//   p += dt*((c1*m)/(c2*sqrt(s) + eps) - wd*p);  g = 0
+//   c1 = 1/(1-beta1^t), c2 = 1/sqrt(1-beta2^t), both formed in double.
+void cpu_update_adam(at::Tensor params, at::Tensor grads, at::Tensor m,
+                     at::Tensor sq, double dt, double scale, double beta1,
+                     double beta2, double eps, double wd, int64_t t) {
+  const int64_t n = params.numel();
+  check_cpu_f32(params, "params", n);
+  check_cpu_f32(grads, "grads", n);
+  check_cpu_f32(m, "m", n);
+  check_cpu_f32(sq, "sq", n);
+  TORCH_CHECK(t >= 1, "t is the 1-based update count");
+  float* pp = params.data_ptr<float>();
+  float* gp = grads.data_ptr<float>();
+  float* mp = m.data_ptr<float>();
+  float* sp = sq.data_ptr<float>();
+  const float fdt = (float)dt, fs = (float)scale, fb1 = (float)beta1,
+              fb2 = (float)beta2, feps = (float)eps, fwd = (float)wd,
+              fo1 = (float)(1.0 - beta1), fo2 = (float)(1.0 - beta2),
+              c1 = (float)(1.0 / (1.0 - std::pow(beta1, (double)t))),
+              c2 = (float)(1.0 / std::sqrt(1.0 - std::pow(beta2, (double)t)));
+  for (int64_t i = 0; i < n; ++i) {
+    const float u = fs * gp[i];
+    const float mi = fb1 * mp[i] + fo1 * u;
+    const float si = fb2 * sp[i] + fo2 * (u * u);
+    mp[i] = mi;
+    sp[i] = si;
+    pp[i] += fdt * ((c1 * mi) / (c2 * std::sqrt(si) + feps) - fwd * pp[i]);
+    gp[i] = 0.f;
+  }
+}
+
 }  // namespace pcnn

@@ -1891,12 +1891,12 @@ __global__ void k_cast_wt_all(const float* __restrict__ params,
 }
 
 // SGD update FUSED with the weight pre-cast: one pass updates every
-// parameter (sgd_apply1: plain or momentum, g = 0) and, for conv-weight
+// parameter (sgd_apply1: plain, momentum or Adam, g = 0) and, for conv-weight
 // elements, emits the next step's bf16 images (wbf/wbfT/wrot/wp8) from the
 // freshly computed value — the separate k_cast_wt_all launch at the next
 // forward is skipped (the engine tracks freshness).
 //
-// The emission block stays written out in k_cast_wt_all and in these two
+// The emission block stays written out in k_cast_wt_all and in these three
 // kernels.  Behind a shared __device__ function, or with the two kernels as
 // wrappers of one body that takes the descriptors, the compiler addresses
 // CastDescs differently: k_cast_wt_all went from 23 to 25 VGPRs and both
@@ -1908,7 +1908,8 @@ __global__ void k_update_cast_all(float* __restrict__ params,
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float pnew =
-      sgd_apply1<false>(params, grads, (float*)nullptr, i, step, MomArgs{});
+      sgd_apply1<OPT_PLAIN>(params, grads, (float*)nullptr, (float*)nullptr,
+                            i, step, MomArgs{});
   for (int s = 0; s < d.n; ++s) {
     const long long q = i - d.w_off[s];
     if (q < 0 || q >= d.cum[s + 1] - d.cum[s]) continue;
@@ -1941,7 +1942,42 @@ __global__ void k_update_cast_all_mom(float* __restrict__ params,
                                       CastDescs d) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float pnew = sgd_apply1<true>(params, grads, vel, i, 0.f, o);
+  const float pnew =
+      sgd_apply1<OPT_MOM>(params, grads, vel, (float*)nullptr, i, 0.f, o);
+  for (int s = 0; s < d.n; ++s) {
+    const long long q = i - d.w_off[s];
+    if (q < 0 || q >= d.cum[s + 1] - d.cum[s]) continue;
+    const int C = d.C[s];
+    const int kc = (int)(q / C);
+    const int c = (int)(q - (long long)kc * C);
+    const __bf16 v = (__bf16)pnew;
+    wbuf[d.bf_off[s] + q] = v;
+    wbuf[d.bfT_off[s] + (long long)c * d.R[s] + kc] = v;
+    const int Cin = d.Cin[s], K = d.K[s];
+    if (kc < K * K * Cin) {
+      const int ci = kc % Cin;
+      const int p2 = kc / Cin;
+      const int ki = p2 / K, kj = p2 - ki * K;
+      const int col = ((K - 1 - ki) * K + (K - 1 - kj)) * C + c;
+      wbuf[d.rot_off[s] + (long long)ci * (K * K * C) + col] = v;
+      if (d.p8_off[s] >= 0)
+        wbuf[d.p8_off[s] + (long long)c * (K * K * 8) + p2 * 8 + ci] = v;
+    }
+    break;
+  }
+}
+
+// k_update_cast_all with the Adam update (m in vel, s in sq): the bf16 images
+// are cast from the post-Adam value.  A pad row (p = g = m = s = 0) stays 0.
+__global__ void k_update_cast_all_adam(float* __restrict__ params,
+                                       float* __restrict__ grads,
+                                       float* __restrict__ vel,
+                                       float* __restrict__ sq, long long n,
+                                       AdamArgs o, __bf16* __restrict__ wbuf,
+                                       CastDescs d) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float pnew = sgd_apply1<OPT_ADAM>(params, grads, vel, sq, i, 0.f, o);
   for (int s = 0; s < d.n; ++s) {
     const long long q = i - d.w_off[s];
     if (q < 0 || q >= d.cum[s + 1] - d.cum[s]) continue;
@@ -1966,27 +2002,37 @@ __global__ void k_update_cast_all_mom(float* __restrict__ params,
 }
 
 // Generic SGD apply + zero over n params (sgd_apply1).
-template <bool MOM>
+template <int OPT, typename Args>
 __device__ __forceinline__ void update_n_body(float* __restrict__ params,
                                               float* __restrict__ grads,
                                               float* __restrict__ vel,
+                                              float* __restrict__ sq,
                                               long long n, float step,
-                                              const MomArgs& o) {
+                                              const Args& o) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) sgd_apply1<MOM>(params, grads, vel, i, step, o);
+  if (i < n) sgd_apply1<OPT>(params, grads, vel, sq, i, step, o);
 }
 
 __global__ void k_update_n(float* __restrict__ params,
                            float* __restrict__ grads, long long n,
                            float step) {
-  update_n_body<false>(params, grads, nullptr, n, step, MomArgs{});
+  update_n_body<OPT_PLAIN>(params, grads, nullptr, nullptr, n, step,
+                           MomArgs{});
 }
 
 __global__ void k_update_n_mom(float* __restrict__ params,
                                float* __restrict__ grads,
                                float* __restrict__ vel, long long n,
                                MomArgs o) {
-  update_n_body<true>(params, grads, vel, n, 0.f, o);
+  update_n_body<OPT_MOM>(params, grads, vel, nullptr, n, 0.f, o);
+}
+
+__global__ void k_update_n_adam(float* __restrict__ params,
+                                float* __restrict__ grads,
+                                float* __restrict__ vel,
+                                float* __restrict__ sq, long long n,
+                                AdamArgs o) {
+  update_n_body<OPT_ADAM>(params, grads, vel, sq, n, 0.f, o);
 }
 
 // MFMA layout self-test: D[16][16] = A[16][32] @ B[32][16], plain fp32 I/O.
@@ -2162,16 +2208,22 @@ int pcnn_deep_cast_all(const float* params, void* wbuf,
   return (int)hipGetLastError();
 }
 
-// SGD update + weight pre-cast (k_update_cast_all, or k_update_cast_all_mom
-// when opt->vel is set: the images are then cast from the post-momentum
-// value).
+// Update + weight pre-cast (k_update_cast_all, or k_update_cast_all_mom /
+// k_update_cast_all_adam by opt_select: the images are then cast from the
+// post-momentum / post-Adam value).
 int pcnn_deep_update_cast(float* params, float* grads, long long n,
                           const pcnn_opt* opt, void* wbuf,
                           const pcnn_cast_desc* desc, void* stream) {
   CastDescs d;
   if (opt == nullptr || !fill_cast_descs(desc, d)) return -2;
   dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  if (opt->vel != nullptr)
+  const int sel = opt_select(opt);
+  if (sel < 0) return -2;
+  if (sel == OPT_ADAM)
+    hipLaunchKernelGGL(k_update_cast_all_adam, grid, block, 0,
+                       (hipStream_t)stream, params, grads, opt->vel, opt->sq,
+                       n, adam_args(opt), (__bf16*)wbuf, d);
+  else if (sel == OPT_MOM)
     hipLaunchKernelGGL(k_update_cast_all_mom, grid, block, 0,
                        (hipStream_t)stream, params, grads, opt->vel, n,
                        mom_args(opt), (__bf16*)wbuf, d);
@@ -2427,7 +2479,12 @@ int pcnn_deep_update(float* params, float* grads, long long n,
                      const pcnn_opt* opt, void* stream) {
   if (opt == nullptr) return -2;
   dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  if (opt->vel != nullptr)
+  const int sel = opt_select(opt);
+  if (sel < 0) return -2;
+  if (sel == OPT_ADAM)
+    hipLaunchKernelGGL(k_update_n_adam, grid, block, 0, (hipStream_t)stream,
+                       params, grads, opt->vel, opt->sq, n, adam_args(opt));
+  else if (sel == OPT_MOM)
     hipLaunchKernelGGL(k_update_n_mom, grid, block, 0, (hipStream_t)stream,
                        params, grads, opt->vel, n, mom_args(opt));
   else

@@ -58,9 +58,11 @@
 //
 // Every kernel that applies the update (k_update, k_wgrad_update,
 // k_reduce_update) has a _mom twin with momentum / Nesterov / weight decay
-// and an fp32 velocity bucket; the two are instantiations of one body with a
-// compile-time MOM flag (sgd_update.h), and the plain kernels are what runs
-// when the optimizer is the default one.
+// and an fp32 velocity bucket, and an _adam twin (Adam with decoupled weight
+// decay, fp32 first- and second-moment buckets); the three are
+// instantiations of one body with a compile-time OPT selector
+// (sgd_update.h), and the plain kernels are what runs when the optimizer is
+// the default one.
 //
 // Numerics: activations AND the large conv preact gradient (dz1) are
 // stored bf16/fp16/fp32 (template); ALL arithmetic is fp32 in
@@ -1244,39 +1246,41 @@ __device__ __forceinline__ bool arrive_is_last(int* __restrict__ ticket) {
 
 // SGD apply + gradient zeroing over the whole bucket by ONE 256-thread
 // block (the last arriver): sgd_apply4 / sgd_apply1 in the same float4 split
-// as k_update, 585 vectors + a 3-float scalar tail.  With MOM the block is
-// the only reader and writer of vel in the launch.  vel was written by the
-// last arriver of the previous launch with plain stores and has crossed a
-// kernel boundary since, exactly like params: plain loads and stores, no
-// fences beyond the ticket's.
-template <bool MOM>
+// as k_update, 585 vectors + a 3-float scalar tail.  Under OPT_MOM the block
+// is the only reader and writer of vel in the launch.  vel was written by
+// the last arriver of the previous launch with plain stores and has crossed
+// a kernel boundary since, exactly like params: plain loads and stores, no
+// fences beyond the ticket's.  The same holds for Adam's two buckets (m in
+// vel, s in sq) under OPT_ADAM.
+template <int OPT, typename Args>
 __device__ __forceinline__ void update_tail(float* __restrict__ params,
                                             float* __restrict__ grads,
                                             float* __restrict__ vel,
-                                            float step, const MomArgs& o) {
+                                            float* __restrict__ sq,
+                                            float step, const Args& o) {
   constexpr int NV = N_PARAMS / 4;
   for (int i4 = threadIdx.x; i4 < NV; i4 += 256)
-    sgd_apply4<MOM>(params, grads, vel, i4 * 4, step, o);
+    sgd_apply4<OPT>(params, grads, vel, sq, i4 * 4, step, o);
   const int u = NV * 4 + threadIdx.x;
-  if (u < N_PARAMS) sgd_apply1<MOM>(params, grads, vel, u, step, o);
+  if (u < N_PARAMS) sgd_apply1<OPT>(params, grads, vel, sq, u, step, o);
 }
 
 // Weight gradients with the SGD update as the tail of the same launch
 // (two-launch training step).  Gradient code is wgrad_body, unchanged; the
 // block that arrives last applies the update, zeroes the bucket and resets
 // the ticket for the next launch.
-template <typename act_t, bool MOM>
+template <typename act_t, int OPT, typename Args>
 __device__ __forceinline__ void wgrad_update_body(
     const act_t* __restrict__ x, const act_t* __restrict__ a1g,
     const act_t* __restrict__ a2g, const float* __restrict__ dzg,
     const float* __restrict__ dz2g, const act_t* __restrict__ dz1g,
     float* __restrict__ grads, int B, int GC, int GS, int FS, int roles,
     float* __restrict__ params, float step, float* __restrict__ vel,
-    const MomArgs& o, int* __restrict__ ticket) {
+    float* __restrict__ sq, const Args& o, int* __restrict__ ticket) {
   wgrad_body<act_t, true>(x, a1g, a2g, dzg, dz2g, dz1g, grads, B, GC, GS,
                           FS, roles);
   if (!arrive_is_last(ticket)) return;
-  update_tail<MOM>(params, grads, vel, step, o);
+  update_tail<OPT>(params, grads, vel, sq, step, o);
   if (threadIdx.x == 0)
     __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -1289,8 +1293,22 @@ __global__ __launch_bounds__(256) void k_wgrad_update_mom(
     float* __restrict__ grads, int B, int GC, int GS, int FS, int roles,
     float* __restrict__ params, float* __restrict__ vel, MomArgs o,
     int* __restrict__ ticket) {
-  wgrad_update_body<act_t, true>(x, a1g, a2g, dzg, dz2g, dz1g, grads, B, GC,
-                                 GS, FS, roles, params, 0.f, vel, o, ticket);
+  wgrad_update_body<act_t, OPT_MOM>(x, a1g, a2g, dzg, dz2g, dz1g, grads, B,
+                                    GC, GS, FS, roles, params, 0.f, vel,
+                                    nullptr, o, ticket);
+}
+
+template <typename act_t>
+__global__ __launch_bounds__(256) void k_wgrad_update_adam(
+    const act_t* __restrict__ x, const act_t* __restrict__ a1g,
+    const act_t* __restrict__ a2g, const float* __restrict__ dzg,
+    const float* __restrict__ dz2g, const act_t* __restrict__ dz1g,
+    float* __restrict__ grads, int B, int GC, int GS, int FS, int roles,
+    float* __restrict__ params, float* __restrict__ vel,
+    float* __restrict__ sq, AdamArgs o, int* __restrict__ ticket) {
+  wgrad_update_body<act_t, OPT_ADAM>(x, a1g, a2g, dzg, dz2g, dz1g, grads, B,
+                                     GC, GS, FS, roles, params, 0.f, vel, sq,
+                                     o, ticket);
 }
 
 template <typename act_t>
@@ -1300,40 +1318,47 @@ __global__ __launch_bounds__(256) void k_wgrad_update(
     const float* __restrict__ dz2g, const act_t* __restrict__ dz1g,
     float* __restrict__ grads, int B, int GC, int GS, int FS, int roles,
     float* __restrict__ params, float step, int* __restrict__ ticket) {
-  wgrad_update_body<act_t, false>(x, a1g, a2g, dzg, dz2g, dz1g, grads, B, GC,
-                                  GS, FS, roles, params, step, nullptr,
-                                  MomArgs{}, ticket);
+  wgrad_update_body<act_t, OPT_PLAIN>(x, a1g, a2g, dzg, dz2g, dz1g, grads, B,
+                                      GC, GS, FS, roles, params, step,
+                                      nullptr, nullptr, MomArgs{}, ticket);
 }
 
 // ---------------------------------------------------------------------------
 // SGD apply + gradient zeroing as a launch of its own: one float4 per thread
 // across the grid (the bucket is 16B-aligned), scalar tail.
 // ---------------------------------------------------------------------------
-template <bool MOM>
+template <int OPT, typename Args>
 __device__ __forceinline__ void update_body(float* __restrict__ params,
                                             float* __restrict__ grads,
                                             float* __restrict__ vel,
-                                            float step, const MomArgs& o) {
+                                            float* __restrict__ sq,
+                                            float step, const Args& o) {
   const int i4 = blockIdx.x * 256 + threadIdx.x;
   const int i = i4 * 4;
   if (i + 3 < N_PARAMS) {
-    sgd_apply4<MOM>(params, grads, vel, i, step, o);
+    sgd_apply4<OPT>(params, grads, vel, sq, i, step, o);
   } else if (i < N_PARAMS) {
     for (int u = i; u < N_PARAMS; ++u)
-      sgd_apply1<MOM>(params, grads, vel, u, step, o);
+      sgd_apply1<OPT>(params, grads, vel, sq, u, step, o);
   }
 }
 
 __global__ __launch_bounds__(256) void k_update(float* __restrict__ params,
                                                 float* __restrict__ grads,
                                                 float step) {
-  update_body<false>(params, grads, nullptr, step, MomArgs{});
+  update_body<OPT_PLAIN>(params, grads, nullptr, nullptr, step, MomArgs{});
 }
 
 __global__ __launch_bounds__(256) void k_update_mom(
     float* __restrict__ params, float* __restrict__ grads,
     float* __restrict__ vel, MomArgs o) {
-  update_body<true>(params, grads, vel, 0.f, o);
+  update_body<OPT_MOM>(params, grads, vel, nullptr, 0.f, o);
+}
+
+__global__ __launch_bounds__(256) void k_update_adam(
+    float* __restrict__ params, float* __restrict__ grads,
+    float* __restrict__ vel, float* __restrict__ sq, AdamArgs o) {
+  update_body<OPT_ADAM>(params, grads, vel, sq, 0.f, o);
 }
 
 
@@ -1363,15 +1388,16 @@ constexpr int INBLOCK_MAX_B = 256;
 // (k_fwdbwd<.., INBLOCK>), 1 = pair (k_fwdbwd_pair).
 constexpr int INBLOCK_DEFAULT_VARIANT = 1;
 
-// MOM selects the apply at the end and nothing else: the plain kernel is the
-// MOM=false instantiation with vel and o unused, the momentum kernel has the
-// owner lane (sub == 0) do the velocity read-modify-write and the parameter
-// store after the same fixed shuffle.
-template <typename act_t, bool MOM>
+// OPT selects the apply at the end and nothing else: the plain kernel is the
+// OPT_PLAIN instantiation with vel, sq and o unused; the momentum and Adam
+// kernels have the owner lane (sub == 0) do the read-modify-write of their
+// state (vel; m in vel and s in sq) and the parameter store after the same
+// fixed shuffle.
+template <typename act_t, int OPT, typename Args>
 __device__ __forceinline__ void reduce_update_body(
     const float* __restrict__ gslab, const act_t* __restrict__ a2g,
     const float* __restrict__ dzg, float* __restrict__ params, float step,
-    int B, float* __restrict__ vel, const MomArgs& o) {
+    int B, float* __restrict__ vel, float* __restrict__ sq, const Args& o) {
   const int p = blockIdx.x * RU_PARAMS_PER_BLOCK + (threadIdx.x >> 2);
   const int sub = threadIdx.x & (RU_LANES - 1);
   // Lanes past the last parameter redo the last one and do not store: the
@@ -1427,7 +1453,12 @@ __device__ __forceinline__ void reduce_update_body(
   acc += __shfl_xor(acc, 1, RU_LANES);
   acc += __shfl_xor(acc, 2, RU_LANES);
   if (sub == 0 && p < N_PARAMS) {
-    if constexpr (MOM) {
+    if constexpr (OPT == OPT_ADAM) {
+      float m = vel[p], s = sq[p];
+      params[p] = adam_apply(params[p], acc, m, s, o);
+      vel[p] = m;
+      sq[p] = s;
+    } else if constexpr (OPT == OPT_MOM) {
       float v = vel[p];
       params[p] = mom_apply(params[p], acc, v, o);
       vel[p] = v;
@@ -1442,8 +1473,8 @@ __global__ __launch_bounds__(256) void k_reduce_update(
     const float* __restrict__ gslab, const act_t* __restrict__ a2g,
     const float* __restrict__ dzg, float* __restrict__ params, float step,
     int B) {
-  reduce_update_body<act_t, false>(gslab, a2g, dzg, params, step, B, nullptr,
-                                   MomArgs{});
+  reduce_update_body<act_t, OPT_PLAIN>(gslab, a2g, dzg, params, step, B,
+                                       nullptr, nullptr, MomArgs{});
 }
 
 template <typename act_t>
@@ -1451,7 +1482,17 @@ __global__ __launch_bounds__(256) void k_reduce_update_mom(
     const float* __restrict__ gslab, const act_t* __restrict__ a2g,
     const float* __restrict__ dzg, float* __restrict__ params,
     float* __restrict__ vel, MomArgs o, int B) {
-  reduce_update_body<act_t, true>(gslab, a2g, dzg, params, 0.f, B, vel, o);
+  reduce_update_body<act_t, OPT_MOM>(gslab, a2g, dzg, params, 0.f, B, vel,
+                                     nullptr, o);
+}
+
+template <typename act_t>
+__global__ __launch_bounds__(256) void k_reduce_update_adam(
+    const float* __restrict__ gslab, const act_t* __restrict__ a2g,
+    const float* __restrict__ dzg, float* __restrict__ params,
+    float* __restrict__ vel, float* __restrict__ sq, AdamArgs o, int B) {
+  reduce_update_body<act_t, OPT_ADAM>(gslab, a2g, dzg, params, 0.f, B, vel,
+                                      sq, o);
 }
 
 }  // namespace pcnn
@@ -1460,8 +1501,9 @@ __global__ __launch_bounds__(256) void k_reduce_update_mom(
 // extern "C" launchers, declared in ../pcnn_launch.h (called from the pybind
 // layer and the native tools; no torch headers here).  All return hipError_t
 // as int.  A launcher that applies the update takes the optimizer as a
-// pcnn_opt: vel == NULL launches the plain kernel with opt->step, anything
-// else the _mom kernel.
+// pcnn_opt: kind == 1 launches the _adam kernel; otherwise vel == NULL
+// launches the plain kernel with opt->step, anything else the _mom kernel
+// (opt_select, sgd_update.h).
 // ---------------------------------------------------------------------------
 
 using namespace pcnn;
@@ -1483,7 +1525,7 @@ int launch_fwdbwd_mode(const void* x, const float* params, void* a1, void* a2,
 }
 
 // ticket == nullptr launches the plain k_wgrad; otherwise k_wgrad_update or
-// k_wgrad_update_mom (by opt->vel) with the same grid.
+// k_wgrad_update_mom / k_wgrad_update_adam (by opt_select) with the same grid.
 int launch_wgrad_any(const void* x, const void* a1, const void* a2,
                      const float* dz, const float* dz2, const void* dz1,
                      float* grads, int B, int act, int chunk_imgs, int roles,
@@ -1505,13 +1547,19 @@ int launch_wgrad_any(const void* x, const void* a1, const void* a2,
   if (FS < 1) FS = 1;
   if (FS > 32) FS = 32;
   dim3 grid(C1_CH * GC + GS + FS * FC_BLOCKS), block(256);
+  const int sel = ticket == nullptr ? OPT_PLAIN : opt_select(opt);
+  if (sel < 0) return (int)hipErrorInvalidValue;
   PCNN_DISPATCH(act, {
     const act_t *xs = (const act_t*)x, *a1s = (const act_t*)a1,
                 *a2s = (const act_t*)a2, *dz1s = (const act_t*)dz1;
     if (ticket == nullptr)
       hipLaunchKernelGGL((k_wgrad<act_t>), grid, block, 0, s, xs, a1s, a2s,
                          dz, dz2, dz1s, grads, B, GC, GS, FS, roles);
-    else if (opt->vel != nullptr)
+    else if (sel == OPT_ADAM)
+      hipLaunchKernelGGL((k_wgrad_update_adam<act_t>), grid, block, 0, s, xs,
+                         a1s, a2s, dz, dz2, dz1s, grads, B, GC, GS, FS, roles,
+                         params, opt->vel, opt->sq, adam_args(opt), ticket);
+    else if (sel == OPT_MOM)
       hipLaunchKernelGGL((k_wgrad_update_mom<act_t>), grid, block, 0, s, xs,
                          a1s, a2s, dz, dz2, dz1s, grads, B, GC, GS, FS, roles,
                          params, opt->vel, mom_args(opt), ticket);
@@ -1564,7 +1612,12 @@ int pcnn_launch_update(float* params, float* grads, const pcnn_opt* opt,
                        void* stream) {
   if (opt == nullptr) return (int)hipErrorInvalidValue;
   dim3 grid((N_PARAMS / 4 + 255) / 256), block(256);
-  if (opt->vel != nullptr)
+  const int sel = opt_select(opt);
+  if (sel < 0) return (int)hipErrorInvalidValue;
+  if (sel == OPT_ADAM)
+    hipLaunchKernelGGL(k_update_adam, grid, block, 0, (hipStream_t)stream,
+                       params, grads, opt->vel, opt->sq, adam_args(opt));
+  else if (sel == OPT_MOM)
     hipLaunchKernelGGL(k_update_mom, grid, block, 0, (hipStream_t)stream,
                        params, grads, opt->vel, mom_args(opt));
   else
@@ -1573,7 +1626,7 @@ int pcnn_launch_update(float* params, float* grads, const pcnn_opt* opt,
   return (int)hipGetLastError();
 }
 
-// Weight gradients + SGD update in one launch (k_wgrad_update[_mom]).
+// Weight gradients + update in one launch (k_wgrad_update[_mom|_adam]).
 int pcnn_launch_wgrad_update(const void* x, const void* a1, const void* a2,
                              const float* dz, const float* dz2,
                              const void* dz1, float* grads, float* params,
@@ -1633,7 +1686,8 @@ int pcnn_launch_fwdbwd_inblock(const void* x, const float* params, void* a2,
   return (int)hipGetLastError();
 }
 
-// Second kernel of the in-block weight-grad step (k_reduce_update[_mom]).
+// Second kernel of the in-block weight-grad step
+// (k_reduce_update[_mom|_adam]).
 int pcnn_launch_reduce_update(const float* gslab, const void* a2,
                               const float* dz, float* params,
                               const pcnn_opt* opt, int B, int act,
@@ -1642,7 +1696,14 @@ int pcnn_launch_reduce_update(const float* gslab, const void* a2,
     return (int)hipErrorInvalidValue;
   dim3 grid(RU_BLOCKS), block(256);
   hipStream_t s = (hipStream_t)stream;
-  if (opt->vel != nullptr)
+  const int sel = opt_select(opt);
+  if (sel < 0) return (int)hipErrorInvalidValue;
+  if (sel == OPT_ADAM)
+    PCNN_DISPATCH(act, hipLaunchKernelGGL(
+                           (k_reduce_update_adam<act_t>), grid, block, 0, s,
+                           gslab, (const act_t*)a2, dz, params, opt->vel,
+                           opt->sq, adam_args(opt), B));
+  else if (sel == OPT_MOM)
     PCNN_DISPATCH(act, hipLaunchKernelGGL(
                            (k_reduce_update_mom<act_t>), grid, block, 0, s,
                            gslab, (const act_t*)a2, dz, params, opt->vel,
@@ -1659,9 +1720,9 @@ int pcnn_launch_reduce_update(const float* gslab, const void* a2,
 int pcnn_inblock_max_batch(void) { return INBLOCK_MAX_B; }
 
 // One whole single-GPU training step with in-block weight grads:
-// k_fwdbwd<INBLOCK> or k_fwdbwd_pair -> k_reduce_update[_mom].  `grads` and
-// `ticket` are only touched by the large-batch fallback and read all-zero /
-// 0 afterwards either way.
+// k_fwdbwd<INBLOCK> or k_fwdbwd_pair -> k_reduce_update[_mom|_adam].  `grads`
+// and `ticket` are only touched by the large-batch fallback and read
+// all-zero / 0 afterwards either way.
 int pcnn_launch_step_inblock(const void* x, float* params, void* a1, void* a2,
                              float* y, float* dz, float* dz2, void* dz1,
                              const int* labels, float* loss_accum,

@@ -22,12 +22,26 @@ extern "C" {
  * by the caller (the launchers never recompute it); the other fields are
  * ignored.  vel != NULL: the momentum kernels, u = scale*g - wd*p;
  * v = mu*v + u; p += dt*v (nesterov: p += dt*(u + mu*v)); `step` is ignored.
- * vel is the fp32 velocity bucket in the layout of params. */
+ * vel is the fp32 velocity bucket in the layout of params.
+ *
+ * kind == 1: the Adam kernels (decoupled weight decay), whatever vel says:
+ * u = scale*g; m = beta1*m + (1-beta1)*u; s = beta2*s + (1-beta2)*u*u;
+ * p += dt*((c1*m)/(c2*sqrt(s) + eps) - wd*p).  vel carries m, mu carries
+ * beta1, sq is s (fp32, layout of params); both buckets are required.  The
+ * caller computes per update, in double, c1 = 1/(1-beta1^t) and
+ * c2 = 1/sqrt(1-beta2^t) for the 1-based update count t, and omb1 = 1-beta1,
+ * omb2 = 1-beta2 (1.f - beta2 in float would carry beta2's own rounding).
+ * `step` and `nesterov` are ignored.  The fields from `kind` on were
+ * appended: an initialiser that stops at vel leaves them zero, kind 0. */
 typedef struct pcnn_opt {
   float step;
   float scale, dt, mu, wd;
   int nesterov;
   float* vel;
+  int kind;
+  float* sq;
+  float beta2, eps, c1, c2;
+  float omb1, omb2;
 } pcnn_opt;
 
 const char* pcnn_hip_error_string(int err);

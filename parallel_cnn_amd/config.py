@@ -34,10 +34,46 @@ class TrainConfig:
     momentum: float = 0.0
     weight_decay: float = 0.0
     nesterov: bool = False
+    # optimizer: sgd (everything above) | adam.  Adam with decoupled weight
+    # decay, for the 1-based update count t: u = scale*g;
+    # m = beta1*m + (1-beta1)*u; s = beta2*s + (1-beta2)*u*u;
+    # p += dt*(mhat/(sqrt(shat) + adam_eps) - weight_decay*p), mhat and shat
+    # bias-corrected by 1/(1-beta^t).  momentum and nesterov must stay off.
+    optimizer: str = "sgd"
+    beta1: float = 0.9
+    beta2: float = 0.999
+    adam_eps: float = 1e-8
+
+    def uses_adam(self) -> bool:
+        """True when the optimizer is Adam (first- and second-moment
+        buffers, an update counter); validates the optimizer fields
+        (ValueError)."""
+        if self.optimizer not in ("sgd", "adam"):
+            raise ValueError(
+                f"optimizer must be sgd or adam, got {self.optimizer!r}")
+        for name in ("beta1", "beta2"):
+            if not 0.0 <= getattr(self, name) < 1.0:
+                raise ValueError(
+                    f"{name} must be in [0, 1), got {getattr(self, name)}")
+        if not self.adam_eps > 0.0:
+            raise ValueError(f"adam_eps must be > 0, got {self.adam_eps}")
+        if self.weight_decay < 0.0:
+            raise ValueError(
+                f"weight_decay must be >= 0, got {self.weight_decay}")
+        if self.optimizer != "adam":
+            return False
+        if self.momentum != 0.0 or self.nesterov:
+            raise ValueError(
+                "optimizer adam excludes momentum and nesterov (beta1 is "
+                "its momentum)")
+        return True
 
     def uses_momentum(self) -> bool:
-        """True when the optimizer needs the velocity buffer; validates the
-        three optimizer fields (ValueError)."""
+        """True when the sgd optimizer needs the velocity buffer; validates
+        the optimizer fields (ValueError).  False under adam, whose state
+        uses_adam() reports."""
+        if self.uses_adam():
+            return False
         if not 0.0 <= self.momentum < 1.0:
             raise ValueError(
                 f"momentum must be in [0, 1), got {self.momentum}")

@@ -12,7 +12,8 @@ pool wgrad+bwd (dapre in place) and implicit dgrad-as-conv GEMMs
 (rotated weight image, sigmoid-bwd epilogue, writing dppre[i-1]
 directly); then EVERY stage's conv wgrad GEMM in ONE k_wgrad_multi
 launch with the bias colsums folded in}; one fused DP all-reduce of the
-flat gradient bucket; SGD update fused with the next step's weight cast.
+flat gradient bucket; SGD (or momentum, or Adam) update fused with the next
+step's weight cast.
 deep_implicit=False keeps the round-1 materialized-cols path.
 """
 from __future__ import annotations
@@ -206,6 +207,14 @@ class DeepTrainer:
         self.vel: Optional[torch.Tensor] = (
             torch.zeros_like(self.model.params) if cfg.uses_momentum()
             else None)
+        # Adam: the first moment lives in vel, the second in sq (both None
+        # otherwise); opt_step counts the updates applied so far, whatever
+        # the optimizer, and is Adam's bias-correction clock
+        self.sq: Optional[torch.Tensor] = None
+        if cfg.uses_adam():
+            self.vel = torch.zeros_like(self.model.params)
+            self.sq = torch.zeros_like(self.model.params)
+        self.opt_step = 0
         act_map = {"bf16": torch.bfloat16, "fp16": torch.float16,
                    "fp32": torch.float32}
         self.act_dtype = (act_map[cfg.act_dtype] if backend == "hip"
@@ -267,8 +276,16 @@ class DeepTrainer:
     def _hip_update(self, scale: float) -> None:
         """SGD update fused with the next step's weight cast."""
         d = self.ws.cast_desc
-        if self.vel is not None:
-            c = self.cfg
+        c = self.cfg
+        self.opt_step += 1
+        if self.sq is not None:
+            self._C.deep_update_cast_adam(
+                self.model.params, self.model.grads, self.vel, self.sq, c.dt,
+                scale, c.beta1, c.beta2, c.adam_eps, c.weight_decay,
+                self.opt_step, self.ws.wbuf, d["R"], d["C"], d["K"],
+                d["Cin"], d["w_off"], d["bf_off"], d["bfT_off"],
+                d["rot_off"], d["p8_off"], native.current_stream_handle())
+        elif self.vel is not None:
             self._C.deep_update_cast_momentum(
                 self.model.params, self.model.grads, self.vel, c.dt, scale,
                 c.momentum, c.weight_decay, c.nesterov, self.ws.wbuf,
@@ -534,9 +551,16 @@ class DeepTrainer:
         provided for the small-batch regime where Python launch overhead
         binds, and as the capture-compatibility check for the step.
         Same shape as the LeNet trainer's capture: warmup on a side
-        stream with the training state snapshotted/restored."""
+        stream with the training state snapshotted/restored.  Not available
+        under Adam, whose bias corrections are kernel arguments that change
+        with every update."""
         if self.backend != "hip":
             raise RuntimeError("graph capture requires the hip backend")
+        if self.sq is not None:
+            raise RuntimeError(
+                "graph capture is not available with optimizer adam: a "
+                "captured graph bakes its kernel arguments, and the bias "
+                "corrections c1, c2 change with every update")
         if self.cfg.grad_accum != 1:
             raise RuntimeError("graph capture assumes grad_accum == 1")
         if pdist.is_distributed() and \
@@ -551,6 +575,7 @@ class DeepTrainer:
         params0 = self.model.params.clone()
         grads0 = self.model.grads.clone()
         vel0 = self.vel.clone() if self.vel is not None else None
+        opt_step0 = self.opt_step
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -567,6 +592,7 @@ class DeepTrainer:
                 self.vel.copy_(vel0)
             self.ws.loss_accum.zero_()
             self.ws.correct_accum.zero_()
+        self.opt_step = opt_step0
         # the captured graph contains NO cast (warmup left wbuf fresh at
         # capture); refresh it for the restored params before any replay
         self._hip_cast_weights(force=True)
@@ -583,6 +609,7 @@ class DeepTrainer:
         self._gx.copy_(x.view(self._gx.shape), non_blocking=True)
         self._gl.copy_(labels, non_blocking=True)
         self._graph.replay()
+        self.opt_step += 1
         self._samples_seen += x.shape[0] * self.ctx.world_size
         self.global_step += 1
 
@@ -628,8 +655,14 @@ class DeepTrainer:
             self.model.grads += grads
             if apply_update:
                 pdist.allreduce_grads(self.model.grads)
-                if self.vel is not None:
-                    c = self.cfg
+                self.opt_step += 1
+                c = self.cfg
+                if self.sq is not None:
+                    torch_ref.update_adam(
+                        self.model.params, self.model.grads, self.vel,
+                        self.sq, c.dt, scale, c.beta1, c.beta2, c.adam_eps,
+                        c.weight_decay, self.opt_step)
+                elif self.vel is not None:
                     torch_ref.update_momentum(
                         self.model.params, self.model.grads, self.vel, c.dt,
                         scale, c.momentum, c.weight_decay, c.nesterov)

@@ -14,8 +14,9 @@ Backends:
 
 A training step is: fused fwd+bwd-data -> weight-grad -> [RCCL all-reduce of
 the flat gradient bucket] -> fused SGD update (with momentum / Nesterov /
-weight decay and a velocity buffer when the config asks for them; the
-momentum variant of the same kernel at every update site).  Loss (sum over
+weight decay and a velocity buffer when the config asks for them, or Adam
+with decoupled weight decay and two moment buffers; the momentum or Adam
+variant of the same kernel at every update site).  Loss (sum over
 samples of ||onehot - y||_2, the reference's metric) accumulates device-side
 and is only synced on readout.
 """
@@ -83,6 +84,14 @@ class Trainer:
         self.vel: Optional[torch.Tensor] = (
             torch.zeros_like(self.model.params) if cfg.uses_momentum()
             else None)
+        # Adam: the first moment lives in vel, the second in sq (both None
+        # otherwise); opt_step counts the updates applied so far, whatever
+        # the optimizer, and is Adam's bias-correction clock
+        self.sq: Optional[torch.Tensor] = None
+        if cfg.uses_adam():
+            self.vel = torch.zeros_like(self.model.params)
+            self.sq = torch.zeros_like(self.model.params)
+        self.opt_step = 0
         act_map = {"bf16": torch.bfloat16, "fp16": torch.float16,
                    "fp32": torch.float32}
         act_dtype = (act_map[cfg.act_dtype] if self.backend == "hip"
@@ -155,6 +164,14 @@ class Trainer:
     def _step_inblock(self, x: torch.Tensor, labels: torch.Tensor, B: int,
                       stream: int) -> None:
         m, w = self.model, self.ws
+        self.opt_step += 1
+        if self.sq is not None:
+            self._C.hip_step_inblock_adam(
+                x, m.params, self.vel, self.sq, w.a1, w.a2, w.y, w.dz, w.dz2,
+                w.dz1, labels, w.loss_accum, m.grads, w.ticket, w.gslab,
+                *self._adam_args(B), B, self.cfg.wgrad_chunk, stream,
+                self._pool_mode, self._loss_mode, self._inblock_variant)
+            return
         if self.vel is not None:
             self._C.hip_step_inblock_momentum(
                 x, m.params, self.vel, w.a1, w.a2, w.y, w.dz, w.dz2, w.dz1,
@@ -184,10 +201,22 @@ class Trainer:
         return (c.dt, self._update_scale(local_batch), c.momentum,
                 c.weight_decay, c.nesterov)
 
+    def _adam_args(self, local_batch: int):
+        """(dt, scale, beta1, beta2, eps, wd, t) as every Adam binding takes
+        them, after m and sq; t is the 1-based count of the update being
+        applied, so opt_step advances BEFORE this is read."""
+        c = self.cfg
+        return (c.dt, self._update_scale(local_batch), c.beta1, c.beta2,
+                c.adam_eps, c.weight_decay, self.opt_step)
+
     def _hip_apply_update(self, B: int, stream: int) -> None:
         """The stand-alone update launch of the 3-launch step."""
         m = self.model
-        if self.vel is not None:
+        self.opt_step += 1
+        if self.sq is not None:
+            self._C.hip_update_adam(m.params, m.grads, self.vel, self.sq,
+                                    *self._adam_args(B), stream)
+        elif self.vel is not None:
             self._C.hip_update_momentum(m.params, m.grads, self.vel,
                                         *self._opt_args(B), stream)
         else:
@@ -197,7 +226,13 @@ class Trainer:
     def _hip_wgrad_update(self, x: torch.Tensor, B: int, stream: int) -> None:
         """Weight grads with the update as the tail of the same launch."""
         m, w = self.model, self.ws
-        if self.vel is not None:
+        self.opt_step += 1
+        if self.sq is not None:
+            self._C.hip_wgrad_update_adam(
+                x, w.a1, w.a2, w.dz, w.dz2, w.dz1, m.grads, m.params,
+                self.vel, self.sq, *self._adam_args(B), w.ticket, B,
+                self.cfg.wgrad_chunk, self._wroles, stream)
+        elif self.vel is not None:
             self._C.hip_wgrad_update_momentum(
                 x, w.a1, w.a2, w.dz, w.dz2, w.dz1, m.grads, m.params,
                 self.vel, *self._opt_args(B), w.ticket, B,
@@ -308,7 +343,11 @@ class Trainer:
             self._loss_host += loss
             if apply_update:
                 pdist.allreduce_grads(m.grads)
-                if self.vel is not None:
+                self.opt_step += 1
+                if self.sq is not None:
+                    self._C.cpu_update_adam(m.params, m.grads, self.vel,
+                                            self.sq, *self._adam_args(B))
+                elif self.vel is not None:
                     self._C.cpu_update_momentum(m.params, m.grads, self.vel,
                                                 *self._opt_args(B))
                 else:
@@ -322,7 +361,11 @@ class Trainer:
             m.grads += grads
             if apply_update:
                 pdist.allreduce_grads(m.grads)
-                if self.vel is not None:
+                self.opt_step += 1
+                if self.sq is not None:
+                    torch_ref.update_adam(m.params, m.grads, self.vel,
+                                          self.sq, *self._adam_args(B))
+                elif self.vel is not None:
                     torch_ref.update_momentum(m.params, m.grads, self.vel,
                                               *self._opt_args(B))
                 else:
@@ -363,9 +406,16 @@ class Trainer:
         """Capture one full training step (2 kernels; 3 + the RCCL all-reduce
         when distributed) into a hipGraph; run_steps_pooled then replays it.
         Requires world_size==1 or the nccl/RCCL backend (gloo is host-side,
-        not capturable)."""
+        not capturable).  Not available under Adam: a captured graph bakes
+        its kernel arguments, and Adam's bias corrections change with every
+        update."""
         if self.backend != "hip":
             raise RuntimeError("graph capture requires the hip backend")
+        if self.sq is not None:
+            raise RuntimeError(
+                "graph capture is not available with optimizer adam: a "
+                "captured graph bakes its kernel arguments, and the bias "
+                "corrections c1, c2 change with every update")
         if self.cfg.grad_accum != 1:
             raise RuntimeError("graph capture assumes grad_accum == 1")
         if pdist.is_distributed() and \
@@ -380,6 +430,7 @@ class Trainer:
         params0 = self.model.params.clone()
         grads0 = self.model.grads.clone()
         vel0 = self.vel.clone() if self.vel is not None else None
+        opt_step0 = self.opt_step
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -395,6 +446,7 @@ class Trainer:
             if vel0 is not None:
                 self.vel.copy_(vel0)
             self.ws.loss_accum.zero_()
+        self.opt_step = opt_step0
         torch.cuda.synchronize()
 
     def _graph_body(self, B: int) -> None:
@@ -421,6 +473,7 @@ class Trainer:
         self._gx.copy_(x, non_blocking=True)
         self._gl.copy_(labels, non_blocking=True)
         self._graph.replay()
+        self.opt_step += 1
         self._samples_seen += x.shape[0] * self.ctx.world_size
         self.global_step += 1
 
@@ -440,7 +493,13 @@ class Trainer:
         if self.backend == "hip" and not pdist.is_distributed():
             w = self.ws
             opt = {}
-            if self.vel is not None:
+            if self.sq is not None:
+                c = self.cfg
+                opt = dict(vel=self.vel, sq=self.sq, dt=c.dt,
+                           scale=self._update_scale(B), mu=c.beta1,
+                           beta2=c.beta2, eps=c.adam_eps, wd=c.weight_decay,
+                           t0=self.opt_step)
+            elif self.vel is not None:
                 dt, scale, mu, wd, nesterov = self._opt_args(B)
                 opt = dict(vel=self.vel, dt=dt, scale=scale, mu=mu, wd=wd,
                            nesterov=nesterov)
@@ -452,6 +511,7 @@ class Trainer:
                 self._loss_mode, self._fuse,
                 4 if self._use_inblock() else self._fused_step_mode(),
                 w.ticket, w.gslab, variant=self._inblock_variant, **opt)
+            self.opt_step += steps
             self._samples_seen += B * steps
             self.global_step += steps
         else:

@@ -20,6 +20,7 @@ cross-checks in the tests.
 """
 from __future__ import annotations
 
+import math
 from typing import Tuple
 
 import torch
@@ -144,4 +145,21 @@ def update_momentum(params: torch.Tensor, grads: torch.Tensor,
         u = scale * grads - wd * params
         vel.mul_(mu).add_(u)
         params += dt * (u + mu * vel if nesterov else vel)
+        grads.zero_()
+
+
+def update_adam(params: torch.Tensor, grads: torch.Tensor, m: torch.Tensor,
+                sq: torch.Tensor, dt: float, scale: float, beta1: float,
+                beta2: float, eps: float, wd: float, t: int) -> None:
+    """Adam with decoupled weight decay in the ascent convention, i.e.
+    torch.optim.AdamW(lr=dt, betas=(beta1, beta2), eps=eps, weight_decay=wd)
+    fed grad = -scale*grads; t is the 1-based count of this update.  In
+    place on params, m and sq, in their own dtype; zeroes grads."""
+    c1 = 1.0 / (1.0 - beta1 ** t)
+    c2 = 1.0 / math.sqrt(1.0 - beta2 ** t)
+    with torch.no_grad():
+        u = scale * grads
+        m.mul_(beta1).add_((1.0 - beta1) * u)
+        sq.mul_(beta2).add_((1.0 - beta2) * (u * u))
+        params += dt * ((c1 * m) / (c2 * sq.sqrt() + eps) - wd * params)
         grads.zero_()

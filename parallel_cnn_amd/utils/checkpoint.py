@@ -2,7 +2,9 @@
 plus a JSON sidecar with training state for EXACT resume (global step,
 epoch cursor, host/device RNG states — so train(2N epochs) ==
 train(N) -> save -> load -> train(N)).  A non-default optimizer (momentum
-or weight decay) adds its velocity as flat LE fp32 at `path + '.vel'`."""
+or weight decay) adds its velocity as flat LE fp32 at `path + '.vel'`; Adam
+puts its first moment there, its second moment at `path + '.sq'` and its
+update count in the sidecar."""
 from __future__ import annotations
 
 import base64
@@ -49,7 +51,15 @@ def save_checkpoint(trainer, path: str) -> None:
         "rng": _rng_capture(),
     }
     vel = getattr(trainer, "vel", None)
-    if vel is not None:
+    sq = getattr(trainer, "sq", None)
+    if sq is not None:
+        vel.detach().cpu().numpy().astype("<f4").tofile(path + ".vel")
+        sq.detach().cpu().numpy().astype("<f4").tofile(path + ".sq")
+        for key in ("optimizer", "beta1", "beta2", "adam_eps",
+                    "weight_decay"):
+            meta[key] = getattr(trainer.cfg, key)
+        meta["opt_step"] = trainer.opt_step
+    elif vel is not None:
         # non-default optimizer only: the default writes exactly the files
         # and keys it always wrote
         vel.detach().cpu().numpy().astype("<f4").tofile(path + ".vel")
@@ -58,6 +68,17 @@ def save_checkpoint(trainer, path: str) -> None:
         meta["nesterov"] = trainer.cfg.nesterov
     with open(path + ".meta.json", "w") as f:
         json.dump(meta, f, indent=1)
+
+
+def _load_bucket(buf: torch.Tensor, file_path: str, what: str) -> None:
+    import numpy as np
+    arr = np.fromfile(file_path, dtype="<f4")
+    if arr.size != buf.numel():
+        raise ValueError(
+            f"{what} file {file_path!r} has {arr.size} floats, "
+            f"expected {buf.numel()}")
+    with torch.no_grad():
+        buf.copy_(torch.from_numpy(arr.copy()).to(buf.device))
 
 
 def _load_velocity(trainer, path: str) -> None:
@@ -74,14 +95,29 @@ def _load_velocity(trainer, path: str) -> None:
         with torch.no_grad():
             vel.zero_()
         return
-    import numpy as np
-    arr = np.fromfile(vel_path, dtype="<f4")
-    if arr.size != vel.numel():
-        raise ValueError(
-            f"velocity file {vel_path!r} has {arr.size} floats, "
-            f"expected {vel.numel()}")
-    with torch.no_grad():
-        vel.copy_(torch.from_numpy(arr.copy()).to(vel.device))
+    _load_bucket(vel, vel_path, "velocity")
+
+
+def _load_adam_state(trainer, path: str, meta: Optional[dict]) -> None:
+    """Restore Adam's m (`.vel`), s (`.sq`) and update count (sidecar
+    `opt_step`).  A size mismatch raises.  The three only mean something
+    together: if any is missing, Adam restarts from zero moments and update
+    0, with a warning."""
+    missing = [ext for ext in (".vel", ".sq")
+               if not os.path.exists(path + ext)]
+    if meta is None or "opt_step" not in meta:
+        missing.append("opt_step")
+    if missing:
+        print(f"warning: checkpoint {path!r} lacks adam state "
+              f"({', '.join(missing)}); adam restarts from zero moments")
+        with torch.no_grad():
+            trainer.vel.zero_()
+            trainer.sq.zero_()
+        trainer.opt_step = 0
+        return
+    _load_bucket(trainer.vel, path + ".vel", "first-moment")
+    _load_bucket(trainer.sq, path + ".sq", "second-moment")
+    trainer.opt_step = int(meta["opt_step"])
 
 
 def load_checkpoint(trainer, path: str) -> Optional[dict]:
@@ -90,12 +126,17 @@ def load_checkpoint(trainer, path: str) -> Optional[dict]:
     trainer.model.load(path)
     if hasattr(trainer, "invalidate_weight_cache"):
         trainer.invalidate_weight_cache()
-    _load_velocity(trainer, path)
     meta_path = path + ".meta.json"
-    if not os.path.exists(meta_path):
+    meta = None
+    if os.path.exists(meta_path):
+        with open(meta_path) as f:
+            meta = json.load(f)
+    if getattr(trainer, "sq", None) is not None:
+        _load_adam_state(trainer, path, meta)
+    else:
+        _load_velocity(trainer, path)
+    if meta is None:
         return None
-    with open(meta_path) as f:
-        meta = json.load(f)
     if meta.get("n_params") not in (None, int(trainer.model.params.numel())):
         raise ValueError(
             f"checkpoint {path!r} is for a model with {meta['n_params']} "

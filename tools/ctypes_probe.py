@@ -56,11 +56,16 @@ labels = dmalloc(B * 4)
 loss = dmalloc(4)
 
 class PcnnOpt(ctypes.Structure):
-    """pcnn_opt of csrc/pcnn_launch.h; vel = NULL selects plain SGD."""
+    """pcnn_opt of csrc/pcnn_launch.h; kind = 0 and vel = NULL select plain
+    SGD (kind = 1 is Adam, with sq and the fields after it)."""
     _fields_ = [("step", ctypes.c_float), ("scale", ctypes.c_float),
                 ("dt", ctypes.c_float), ("mu", ctypes.c_float),
                 ("wd", ctypes.c_float), ("nesterov", ctypes.c_int),
-                ("vel", ctypes.c_void_p)]
+                ("vel", ctypes.c_void_p), ("kind", ctypes.c_int),
+                ("sq", ctypes.c_void_p), ("beta2", ctypes.c_float),
+                ("eps", ctypes.c_float), ("c1", ctypes.c_float),
+                ("c2", ctypes.c_float), ("omb1", ctypes.c_float),
+                ("omb2", ctypes.c_float)]
 
 
 # argtypes follow the declarations in csrc/pcnn_launch.h one for one
