@@ -48,6 +48,22 @@ class DeepWorkspace:
         ntiles = (st.cout + 63) // 64
         return max(1, min(256, target // (ktiles * ntiles), M // 64))
 
+    @staticmethod
+    def split_need(M: int, N: int, K: int) -> int:
+        """fp32 elements of split-K scratch pcnn_deep_gemm wants for an
+        [M,K]x[K,N] GEMM (0: it would not split).  Mirrors the launcher's
+        policy, K counted in its 32-wide BKC steps: counted in 64s (an
+        earlier BKC) the slab came out half the size whenever the chunk
+        count is limited by the K-tiles, and the launcher, finding the
+        scratch too small, silently ran those GEMMs unsplit."""
+        mn = ((M + 63) // 64) * ((N + 63) // 64)
+        ktiles = (K + 31) // 32
+        if mn >= 768 or ktiles <= 1 or N % 8:
+            return 0
+        ks = min(ktiles, 1024 // mn + 1)
+        tpc = (ktiles + ks - 1) // ks
+        return ((ktiles + tpc - 1) // tpc) * M * N
+
     def __init__(self, model: DeepCNN, max_batch: int, device, act_dtype,
                  implicit: bool = True):
         spec = model.spec
@@ -149,15 +165,7 @@ class DeepWorkspace:
             self.wp8.append(self.wbuf[o3:o3 + n3] if n3 else None)
         # split-K slab scratch (fp32): sized by replaying the launcher's
         # split policy over every GEMM shape this batch size will launch
-        def split_need(M, N, K):
-            mn = ((M + 63) // 64) * ((N + 63) // 64)
-            ktiles = (K + 63) // 64
-            if mn >= 768 or ktiles <= 1 or N % 8:
-                return 0
-            ks = min(ktiles, 1024 // mn + 1)
-            tpc = (ktiles + ks - 1) // ks
-            return ((ktiles + tpc - 1) // tpc) * M * N
-
+        split_need = self.split_need
         need = 0
         for i, st in enumerate(spec.stages):
             M = B * st.h * st.w
@@ -438,6 +446,7 @@ class DeepTrainer:
         # dppre[i-1].  Conv wgrads move to pass 2: each only needs its
         # stage's dapre (stable once written) and its input activation,
         # so all of them batch into ONE launch afterwards.
+        early_done = set()
         for i in range(nstage - 1, -1, -1):
             st = spec.stages[i]
             M = B * st.h * st.w
@@ -463,7 +472,17 @@ class DeepTrainer:
                                       st.h, st.w, st.cout, st.pool_k, st_h)
             dapre = w.acts[i]
             implicit = w.stage_implicit[i]
-            if async_wg:
+            # a materialized stage's dgrad below writes dcols INTO cols[i],
+            # the very buffer its conv wgrad reads as the im2col operand:
+            # that wgrad has to run first, on this stream.  (Batched into
+            # pass 2, or put on the side stream, it read dcols and produced
+            # a wrong conv{i}_w gradient for every i > 0 with
+            # deep_implicit=False.)
+            early = i > 0 and not implicit and not w.stage_pad8[i]
+            if early:
+                self._launch_wgrad_stage(x, B, i, st_h)
+                early_done.add(i)
+            elif async_wg:
                 # this stage's dapre is final: its weight grad can run on
                 # the side stream, concurrent with the rest of the chain
                 self._wev[i].record(main_s)
@@ -506,6 +525,8 @@ class DeepTrainer:
         da, dd, dwv, dbv = [], [], [], []
         Ml, Kl, Nl, MSl, Il, XHl, XWl, XCl, XKl, XPl = ([] for _ in range(10))
         for i, st in enumerate(spec.stages):
+            if i in early_done:
+                continue
             M = B * st.h * st.w
             x_in = x if i == 0 else w.pouts[i - 1]
             if w.stage_pad8[i]:

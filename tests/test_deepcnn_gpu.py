@@ -1,12 +1,16 @@
 """GPU tests for the DeepCNN im2col + MFMA GEMM path."""
 import json
+import os
 import subprocess
 import sys
 
 import pytest
 import torch
 
-from parallel_cnn_amd import _C
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                                os.pardir, "tools"))
+import deep_emul  # noqa: E402  (tools/: shared with tools/fuzz_deep.py)
+from parallel_cnn_amd import _C  # noqa: E402
 from parallel_cnn_amd.config import TrainConfig
 from parallel_cnn_amd.data.mnist import synthetic_images
 from parallel_cnn_amd.engine.deep import DeepTrainer
@@ -89,6 +93,90 @@ def hip_step_pieces(B, act_dtype, device, seed=7, implicit=True):
     return t, x, labels
 
 
+def assert_step_blocks(t, x, labels, what):
+    """Per-block check of one step's parameter move against the float64
+    oracle: ||dp_hip - dp_ref|| <= tol_block * ||dp_ref|| with tol_block =
+    4 x the rounding-emulating oracle's own ratio (tools/deep_emul.py), plus
+    the fp32 quantum of the stored parameter.  Returns the excluded blocks
+    (fp16 only)."""
+    B, spec, act = x.shape[0], t.model.spec, t.cfg.act_dtype
+    p0 = DeepCNN(seed=t.cfg.seed, spec=spec).params
+    g, _, emul = deep_emul.oracle_pair(x.view(B, 32, 32, 3), labels, p0,
+                                       spec, act)
+    dp_ref = t.cfg.dt * (1.0 / B) * g
+    p1 = t.model.params.cpu()
+    fails, excluded = deep_emul.compare_blocks(
+        what, p1.double() - p0.double(), dp_ref, emul, act, spec,
+        floor=deep_emul.step_delta_floor(p1, dp_ref, spec))
+    assert not fails, (what, fails)
+    return excluded
+
+
+def hip_grads(cfg, x, labels):
+    """_hip_forward + _hip_backward on a fresh trainer; the flat gradient
+    bucket (batch sums) read before any all-reduce or update."""
+    t = DeepTrainer(cfg)
+    B = x.shape[0]
+    xb, lb = t.stage_batch(x, labels)
+    t._hip_forward(xb, lb, B, 0)
+    t._hip_backward(xb, B)
+    torch.cuda.synchronize()
+    return t, t.model.grads.cpu().clone()
+
+
+GRAD_CONFIGS = [
+    # channels, implicit, seed (the seeds of the step tests below)
+    ("32,64,64", True, 7), ("32,64,64", False, 7), ("16,32,48", True, 23),
+    ("16,32,32,64", True, 29),
+]
+
+
+@pytest.mark.parametrize("act", ["fp32", "bf16"])
+@pytest.mark.parametrize("channels,implicit,seed", GRAD_CONFIGS)
+def test_hip_grads_per_block(act, channels, implicit, seed, device):
+    """Whole-step gradients block by block, relative L2 against the float64
+    oracle.  The one-step parameter tests cannot see the conv and early pool
+    blocks (their moves are orders below those tolerances); here every
+    block of spec.offsets must land within 4 x the error the number formats
+    alone cause.  Measured ratios: PARITY.md."""
+    B = 8
+    cfg = TrainConfig(batch_size=B, device="cuda", backend="hip",
+                      act_dtype=act, log_interval=0, deep_channels=channels,
+                      deep_implicit=implicit)
+    x, labels = synthetic_images(B, 32, 32, 3, seed=seed, structured=False)
+    t, g_hip = hip_grads(cfg, x, labels)
+    spec = t.model.spec
+    g, _, emul = deep_emul.oracle_pair(x.view(B, 32, 32, 3), labels,
+                                       t.model.params, spec, act)
+    what = f"grads[{act},{channels},implicit={implicit}]"
+    fails, excluded = deep_emul.compare_blocks(what, g_hip, g, emul, act,
+                                               spec)
+    assert not excluded
+    assert not fails, (what, fails)
+
+
+@pytest.mark.parametrize("implicit", [True, False])
+def test_hip_grads_per_block_fp16(implicit, device):
+    """fp16 activation storage, default three-stage config only: the
+    stage-0 pool-preact gradients (~1e-8) lie below fp16's smallest
+    subnormal, so conv0_w / conv0_b are lost in storage (emulated ratio
+    0.18) and are the ONLY blocks excluded; the other 12 must pass."""
+    B = 8
+    cfg = TrainConfig(batch_size=B, device="cuda", backend="hip",
+                      act_dtype="fp16", log_interval=0,
+                      deep_implicit=implicit)
+    x, labels = synthetic_images(B, 32, 32, 3, seed=7, structured=False)
+    t, g_hip = hip_grads(cfg, x, labels)
+    spec = t.model.spec
+    g, _, emul = deep_emul.oracle_pair(x.view(B, 32, 32, 3), labels,
+                                       t.model.params, spec, "fp16")
+    what = f"grads[fp16,32,64,64,implicit={implicit}]"
+    fails, excluded = deep_emul.compare_blocks(what, g_hip, g, emul, "fp16",
+                                               spec)
+    assert excluded == {"conv0_w", "conv0_b"}, excluded
+    assert not fails, (what, fails)
+
+
 @pytest.mark.parametrize("implicit", [True, False])
 def test_hip_step_matches_oracle_fp32(implicit, device):
     """Full fp32-activation training step vs the torchref oracle: the whole
@@ -105,6 +193,8 @@ def test_hip_step_matches_oracle_fp32(implicit, device):
     diff = (t.model.params.cpu() - ref.params).abs()
     rel = diff.max().item()
     assert rel < 5e-3, rel
+    assert not assert_step_blocks(t, x, labels,
+                                  f"step[fp32,implicit={implicit}]")
     lg, n = t.consume_loss()
     assert n == B
     assert abs(lg - loss) < 1e-2 * max(1.0, loss)
@@ -126,6 +216,7 @@ def test_hip_step_matches_oracle_bf16(device):
     diff = (delta_hip - delta_ref).abs().max().item()
     scale = delta_ref.abs().max().item()
     assert diff < 0.1 * max(1e-3, scale), (diff, scale)
+    assert not assert_step_blocks(t, x, labels, "step[bf16]")
     lg, n = t.consume_loss()
     assert abs(lg - loss) < 5e-2 * max(1.0, loss)
 
@@ -144,6 +235,10 @@ def test_hip_step_fp16_close(device):
     diff = (delta_hip - delta_ref).abs().max().item()
     scale = delta_ref.abs().max().item()
     assert diff < 0.1 * max(1e-3, scale), (diff, scale)
+    # this batch's conv0_b sits at the 0.1 exclusion limit (emulated
+    # 0.099): whichever side it falls on, nothing past stage-0 conv may go
+    assert assert_step_blocks(t, x, labels, "step[fp16]") <= \
+        {"conv0_w", "conv0_b"}
 
 
 def test_hip_eval(device):
@@ -308,6 +403,7 @@ def test_custom_channel_widths_gpu(device):
         ref.params += t.cfg.dt * (1.0 / 8) * grads
     diff = (t.model.params.cpu() - ref.params).abs().max().item()
     assert diff < 5e-3, diff
+    assert not assert_step_blocks(t, x, labels, "step[fp32,16,32,48]")
 
 
 def test_four_stage_hip_matches_oracle(device):
@@ -330,6 +426,7 @@ def test_four_stage_hip_matches_oracle(device):
         ref.params += t.cfg.dt * (1.0 / 8) * grads
     diff = (t.model.params.cpu() - ref.params).abs().max().item()
     assert diff < 5e-3, diff
+    assert not assert_step_blocks(t, x, labels, "step[fp32,16,32,32,64]")
 
 
 def test_async_wgrad_mode_matches_multi(device):
