@@ -412,6 +412,14 @@ void reduce_update_impl(const at::Tensor& gslab, const at::Tensor& a2,
             what);
 }
 
+// Plain form (k_reduce_update): params += step * g.
+void hip_reduce_update(at::Tensor gslab, at::Tensor a2, at::Tensor dz,
+                       at::Tensor params, double step, int64_t B,
+                       int64_t stream) {
+  reduce_update_impl(gslab, a2, dz, params, plain_opt(step), B, stream,
+                     "reduce_update");
+}
+
 // Momentum form (k_reduce_update_mom).
 void hip_reduce_update_momentum(at::Tensor gslab, at::Tensor a2,
                                 at::Tensor dz, at::Tensor params,
@@ -980,6 +988,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("vel"), py::arg("dt"), py::arg("scale"), py::arg("mu"),
         py::arg("wd"), py::arg("nesterov"), py::arg("ticket"), py::arg("B"),
         py::arg("chunk_imgs"), py::arg("roles"), py::arg("stream"));
+  m.def("hip_reduce_update", &hip_reduce_update, py::arg("gslab"),
+        py::arg("a2"), py::arg("dz"), py::arg("params"), py::arg("step"),
+        py::arg("B"), py::arg("stream"));
   m.def("hip_reduce_update_momentum", &hip_reduce_update_momentum,
         py::arg("gslab"), py::arg("a2"), py::arg("dz"), py::arg("params"),
         py::arg("vel"), py::arg("dt"), py::arg("scale"), py::arg("mu"),

@@ -45,7 +45,12 @@
 //   2. k_reduce_update — one owner group of 4 lanes per parameter: sums the
 //      slab column or the fc outer product over the batch and applies the
 //      SGD update.  No atomics, no gradient bucket, no ticket, no fences;
-//      results are bit-reproducible.
+//      results are bit-reproducible.  One branch-free path with every
+//      kernel argument and the parameter's state fetched at entry and, up to
+//      64 images, every batch load in flight before the first add: one
+//      memory round trip where there were three (9.56 against 10.15
+//      us/step at bs=64, profiles/r8).  k_fwdbwd_pair was tried the same
+//      way, measured slower and left as it was (profiles/r8 section 5).
 //
 // k_fwdbwd_pair is kernel 1 of that step with two adjacent lanes per pool
 // cell and 512-thread blocks (two waves per SIMD), every global load issued
@@ -1370,14 +1375,33 @@ __global__ __launch_bounds__(256) void k_update_adam(
 //   fc weight (k,m) g = sum_b dz[b][k] * a2[b][m]
 //   fc bias k       g = sum_b dz[b][k]
 //   params[p] += step * g
-// Lane `sub` of a group takes images sub, sub+4, ...; RU_DEPTH of them are
-// loaded before the first is added, with clamped addresses and a select so
-// the loads stay unconditional.  Each lane adds in ascending image order
-// and the group combines with a fixed 2-step xor shuffle, so the result
-// does not depend on which block ran where or when.
+// Lane `sub` of a group takes images sub, sub+4, ...  Each lane adds in
+// ascending image order into one accumulator and the group combines with a
+// fixed 2-step xor shuffle, so the result does not depend on which block ran
+// where or when.
+//
+// The kernel is one dependent chain, so what it costs is the number of
+// memory round trips on that chain, and it is written to have one at B <= 64:
+//   * every kernel argument is fetched at entry, behind one scalar wait;
+//   * params[p] (and vel[p], sq[p]) are loaded at entry, with the clamped
+//     index, next to the first batch loads, not after the shuffle;
+//   * the three cases are one branch-free path: a column pointer and a row
+//     stride select slab column or dz column, and a lane that is not an fc
+//     weight multiplies by 1.0f (fma(d, 1, acc) is d + acc, bit for bit), so
+//     a wave that straddles two cases does not run two load chains;
+//   * a trip is RU_LANES * DEPTH images, loaded with clamped addresses and a
+//     select so the loads stay unconditional; the loads of trip t+1 are
+//     issued before the adds of trip t (trip count is block-uniform).  The
+//     compiler gives trip t+1 the registers of trip t, so those loads still
+//     wait for the oldest data of trip t: B = 256 is about four round trips.
+//     DEPTH is 16, so B <= 64 is a single trip, but 8 up to 32 images:
+//     with depth 16 at B = 16, 24 of a lane's 32 loads are clamped repeats
+//     and the step is 0.27 us slower (8.95 against 8.67, the whole gain at
+//     that size; profiles/r8).
 // ---------------------------------------------------------------------------
 constexpr int RU_LANES = 4;
-constexpr int RU_DEPTH = 8;
+constexpr int RU_DEPTH_SMALL = 8;   // B <= RU_LANES * RU_DEPTH_SMALL
+constexpr int RU_DEPTH = 16;
 constexpr int RU_PARAMS_PER_BLOCK = 256 / RU_LANES;  // 64
 constexpr int RU_BLOCKS =
     (N_PARAMS + RU_PARAMS_PER_BLOCK - 1) / RU_PARAMS_PER_BLOCK;  // 37
@@ -1387,6 +1411,75 @@ constexpr int INBLOCK_MAX_B = 256;
 // Kernel 1 of the in-block step when the caller does not choose: 0 = cell
 // (k_fwdbwd<.., INBLOCK>), 1 = pair (k_fwdbwd_pair).
 constexpr int INBLOCK_DEFAULT_VARIANT = 1;
+
+// Have the optimizer's kernel arguments in scalar registers here (an empty
+// statement that reads them): one fetch at entry instead of one per use.
+__device__ __forceinline__ void ru_fetch_args(const MomArgs& o) {
+  asm volatile("" ::"s"(o.scale), "s"(o.dt), "s"(o.mu), "s"(o.wd),
+               "s"(o.nesterov));
+}
+__device__ __forceinline__ void ru_fetch_args(const AdamArgs& o) {
+  asm volatile("" ::"s"(o.scale), "s"(o.dt), "s"(o.beta1), "s"(o.beta2),
+               "s"(o.eps), "s"(o.wd), "s"(o.c1), "s"(o.c2), "s"(o.omb1),
+               "s"(o.omb2));
+}
+
+// One trip of a lane: images b0, b0 + 4, ..., DEPTH of them.  ru_load only
+// issues the loads (clamped, so unconditional); ru_add applies the selects,
+// d = 0 past the batch and a = 1.0f outside the fc weights, where it adds, so
+// nothing in a load block waits for data.
+template <int DEPTH, typename act_t>
+__device__ __forceinline__ void ru_load(float (&d)[DEPTH], act_t (&a)[DEPTH],
+                                        const float* __restrict__ dcol,
+                                        int dld,
+                                        const act_t* __restrict__ acol,
+                                        int b0, int B) {
+#pragma unroll
+  for (int u = 0; u < DEPTH; ++u) {
+    const int b = b0 + u * RU_LANES;
+    const int bc = b < B ? b : B - 1;
+    d[u] = dcol[(size_t)bc * dld];
+    a[u] = acol[(size_t)bc * FC_IN];
+  }
+}
+template <int DEPTH, typename act_t>
+__device__ __forceinline__ float ru_add(float acc, const float (&d)[DEPTH],
+                                        const act_t (&a)[DEPTH], bool fcw,
+                                        int b0, int B) {
+#pragma unroll
+  for (int u = 0; u < DEPTH; ++u)
+    acc = __builtin_fmaf(b0 + u * RU_LANES < B ? d[u] : 0.f,
+                         fcw ? (float)a[u] : 1.0f, acc);
+  return acc;
+}
+
+// Sum of one lane over its images, ascending, into one accumulator.
+template <int DEPTH, typename act_t>
+__device__ __forceinline__ float ru_sum(const float* __restrict__ dcol,
+                                        int dld,
+                                        const act_t* __restrict__ acol,
+                                        bool fcw, int sub, int B) {
+  constexpr int STEP_B = RU_LANES * DEPTH;
+  float d[DEPTH];
+  act_t a[DEPTH];
+  ru_load<DEPTH>(d, a, dcol, dld, acol, sub, B);
+  __builtin_amdgcn_sched_barrier(0);
+  float acc = 0.f;
+  int base = 0;  // first image of the trip in d, a: block-uniform
+  for (; base + STEP_B < B; base += STEP_B) {
+    float dn[DEPTH];
+    act_t an[DEPTH];
+    ru_load<DEPTH>(dn, an, dcol, dld, acol, base + STEP_B + sub, B);
+    __builtin_amdgcn_sched_barrier(0);
+    acc = ru_add<DEPTH>(acc, d, a, fcw, base + sub, B);
+#pragma unroll
+    for (int u = 0; u < DEPTH; ++u) {
+      d[u] = dn[u];
+      a[u] = an[u];
+    }
+  }
+  return ru_add<DEPTH>(acc, d, a, fcw, base + sub, B);
+}
 
 // OPT selects the apply at the end and nothing else: the plain kernel is the
 // OPT_PLAIN instantiation with vel, sq and o unused; the momentum and Adam
@@ -1398,72 +1491,51 @@ __device__ __forceinline__ void reduce_update_body(
     const float* __restrict__ gslab, const act_t* __restrict__ a2g,
     const float* __restrict__ dzg, float* __restrict__ params, float step,
     int B, float* __restrict__ vel, float* __restrict__ sq, const Args& o) {
+  asm volatile("" ::"s"(gslab), "s"(a2g), "s"(dzg), "s"(params), "s"(B));
+  if constexpr (OPT == OPT_PLAIN) asm volatile("" ::"s"(step));
+  if constexpr (OPT != OPT_PLAIN) {
+    asm volatile("" ::"s"(vel));
+    ru_fetch_args(o);
+  }
+  if constexpr (OPT == OPT_ADAM) asm volatile("" ::"s"(sq));
   const int p = blockIdx.x * RU_PARAMS_PER_BLOCK + (threadIdx.x >> 2);
   const int sub = threadIdx.x & (RU_LANES - 1);
   // Lanes past the last parameter redo the last one and do not store: the
   // whole group stays active for the shuffle.
   const int pc = p < N_PARAMS ? p : N_PARAMS - 1;
-  constexpr int STEP_B = RU_LANES * RU_DEPTH;
-  float acc = 0.f;
-  if (pc < OFF_FW) {
-    for (int b0 = sub; b0 < B; b0 += STEP_B) {
-      float v[RU_DEPTH];
-#pragma unroll
-      for (int u = 0; u < RU_DEPTH; ++u) {
-        const int b = b0 + u * RU_LANES;
-        const int bc = b < B ? b : B - 1;
-        v[u] = gslab[(size_t)bc * GSLAB_LD + pc];
-        if (b >= B) v[u] = 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < RU_DEPTH; ++u) acc += v[u];
-    }
-  } else if (pc < OFF_FB) {
-    const int q = pc - OFF_FW;
-    const int k = q / FC_IN;
-    const int m = q - k * FC_IN;
-    for (int b0 = sub; b0 < B; b0 += STEP_B) {
-      float d[RU_DEPTH], a[RU_DEPTH];
-#pragma unroll
-      for (int u = 0; u < RU_DEPTH; ++u) {
-        const int b = b0 + u * RU_LANES;
-        const int bc = b < B ? b : B - 1;
-        d[u] = dzg[(size_t)bc * FC_OUT + k];
-        a[u] = ldf(a2g + (size_t)bc * FC_IN + m);
-        if (b >= B) d[u] = 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < RU_DEPTH; ++u) acc += d[u] * a[u];
-    }
-  } else {
-    const int k = pc - OFF_FB;
-    for (int b0 = sub; b0 < B; b0 += STEP_B) {
-      float d[RU_DEPTH];
-#pragma unroll
-      for (int u = 0; u < RU_DEPTH; ++u) {
-        const int b = b0 + u * RU_LANES;
-        const int bc = b < B ? b : B - 1;
-        d[u] = dzg[(size_t)bc * FC_OUT + k];
-        if (b >= B) d[u] = 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < RU_DEPTH; ++u) acc += d[u];
-    }
-  }
+  // state of the parameter, in flight together with the first batch loads
+  float pv = params[pc];
+  float mv = 0.f, sv = 0.f;
+  if constexpr (OPT != OPT_PLAIN) mv = vel[pc];
+  if constexpr (OPT == OPT_ADAM) sv = sq[pc];
+  // slab column pc | dz column k of fc weight (k, m) | dz column of fc bias
+  const bool slab = pc < OFF_FW;
+  const bool fcw = !slab && pc < OFF_FB;
+  const int q = fcw ? pc - OFF_FW : 0;
+  const int k = fcw ? q / FC_IN : (slab ? 0 : pc - OFF_FB);
+  const int m = q - (fcw ? k : 0) * FC_IN;
+  const float* dcol = slab ? gslab + pc : dzg + k;
+  const int dld = slab ? GSLAB_LD : FC_OUT;
+  const act_t* acol = a2g + m;
+  float acc = B <= RU_LANES * RU_DEPTH_SMALL
+                  ? ru_sum<RU_DEPTH_SMALL>(dcol, dld, acol, fcw, sub, B)
+                  : ru_sum<RU_DEPTH>(dcol, dld, acol, fcw, sub, B);
+  // consumed here, by every lane, so the state loads stay at the top
+  asm volatile("" : "+v"(pv));
+  if constexpr (OPT != OPT_PLAIN) asm volatile("" : "+v"(mv));
+  if constexpr (OPT == OPT_ADAM) asm volatile("" : "+v"(sv));
   acc += __shfl_xor(acc, 1, RU_LANES);
   acc += __shfl_xor(acc, 2, RU_LANES);
   if (sub == 0 && p < N_PARAMS) {
     if constexpr (OPT == OPT_ADAM) {
-      float m = vel[p], s = sq[p];
-      params[p] = adam_apply(params[p], acc, m, s, o);
-      vel[p] = m;
-      sq[p] = s;
+      params[p] = adam_apply(pv, acc, mv, sv, o);
+      vel[p] = mv;
+      sq[p] = sv;
     } else if constexpr (OPT == OPT_MOM) {
-      float v = vel[p];
-      params[p] = mom_apply(params[p], acc, v, o);
-      vel[p] = v;
+      params[p] = mom_apply(pv, acc, mv, o);
+      vel[p] = mv;
     } else {
-      params[p] += step * acc;
+      params[p] = __builtin_fmaf(step, acc, pv);
     }
   }
 }
