@@ -122,6 +122,17 @@ float* sq_ptr(const at::Tensor& sq, const at::Tensor& params) {
   return sq.data_ptr<float>();
 }
 
+// Loss-scaler state (pcnn_opt.ls_state): PCNN_LS_WORDS device fp32 words, or
+// None / an empty tensor for no loss scaling.
+const float* ls_ptr(const c10::optional<at::Tensor>& ls) {
+  if (!ls.has_value() || ls->numel() == 0) return nullptr;
+  TORCH_CHECK(ls->is_cuda() && ls->scalar_type() == at::kFloat &&
+                  ls->is_contiguous() && ls->numel() == PCNN_LS_WORDS,
+              "ls_state must be a contiguous device fp32 tensor of ",
+              PCNN_LS_WORDS, " words");
+  return ls->data_ptr<float>();
+}
+
 // The optimizer of a launch (pcnn_opt, pcnn_launch.h): the plain bindings
 // pass the pre-multiplied step and no velocity, which selects the plain
 // kernels; the _momentum bindings pass dt and scale apart and the velocity
@@ -636,10 +647,12 @@ void deep_update_cast(at::Tensor params, at::Tensor grads, double step,
                       std::vector<int64_t> bf_off,
                       std::vector<int64_t> bfT_off,
                       std::vector<int64_t> rot_off,
-                      std::vector<int64_t> p8_off, int64_t stream) {
+                      std::vector<int64_t> p8_off, int64_t stream,
+    c10::optional<at::Tensor> ls_state) {
   const CastDesc cd("deep_update_cast", R, C, K, Cin, w_off, bf_off, bfT_off,
                     rot_off, p8_off);
-  const pcnn_opt opt = plain_opt(step);
+  pcnn_opt opt = plain_opt(step);
+  opt.ls_state = ls_ptr(ls_state);
   check_hip(pcnn_deep_update_cast(params.data_ptr<float>(),
                                   grads.data_ptr<float>(), params.numel(),
                                   &opt, wbuf.data_ptr(), &cd.d,
@@ -659,11 +672,13 @@ void deep_update_cast_momentum(at::Tensor params, at::Tensor grads,
                                std::vector<int64_t> bf_off,
                                std::vector<int64_t> bfT_off,
                                std::vector<int64_t> rot_off,
-                               std::vector<int64_t> p8_off, int64_t stream) {
+                               std::vector<int64_t> p8_off, int64_t stream,
+    c10::optional<at::Tensor> ls_state) {
   const CastDesc cd("deep_update_cast_momentum", R, C, K, Cin, w_off, bf_off,
                     bfT_off, rot_off, p8_off);
   TORCH_CHECK(grads.numel() == params.numel(), "grads/params size mismatch");
-  const pcnn_opt opt = momentum_opt(vel, params, dt, scale, mu, wd, nesterov);
+  pcnn_opt opt = momentum_opt(vel, params, dt, scale, mu, wd, nesterov);
+  opt.ls_state = ls_ptr(ls_state);
   check_hip(pcnn_deep_update_cast(params.data_ptr<float>(),
                                   grads.data_ptr<float>(), params.numel(),
                                   &opt, wbuf.data_ptr(), &cd.d,
@@ -683,12 +698,13 @@ void deep_update_cast_adam(at::Tensor params, at::Tensor grads, at::Tensor m,
                            std::vector<int64_t> bf_off,
                            std::vector<int64_t> bfT_off,
                            std::vector<int64_t> rot_off,
-                           std::vector<int64_t> p8_off, int64_t stream) {
+                           std::vector<int64_t> p8_off, int64_t stream,
+    c10::optional<at::Tensor> ls_state) {
   const CastDesc cd("deep_update_cast_adam", R, C, K, Cin, w_off, bf_off,
                     bfT_off, rot_off, p8_off);
   TORCH_CHECK(grads.numel() == params.numel(), "grads/params size mismatch");
-  const pcnn_opt opt =
-      adam_opt(m, sq, params, dt, scale, beta1, beta2, eps, wd, t);
+  pcnn_opt opt = adam_opt(m, sq, params, dt, scale, beta1, beta2, eps, wd, t);
+  opt.ls_state = ls_ptr(ls_state);
   check_hip(pcnn_deep_update_cast(params.data_ptr<float>(),
                                   grads.data_ptr<float>(), params.numel(),
                                   &opt, wbuf.data_ptr(), &cd.d,
@@ -834,7 +850,7 @@ void deep_fc_fwd(at::Tensor flat, at::Tensor fw, at::Tensor fb,
                  at::Tensor labels, at::Tensor y, at::Tensor dz,
                  at::Tensor loss_accum, at::Tensor correct_accum, int64_t B,
                  int64_t FCIN, int64_t NCLS, int64_t mode, int64_t stream,
-                 at::Tensor dflat) {
+                 at::Tensor dflat, c10::optional<at::Tensor> ls_state) {
   check_hip(pcnn_deep_fc_fwd(
                 flat.data_ptr(), fw.data_ptr<float>(), fb.data_ptr<float>(),
                 labels.data_ptr<int>(),
@@ -844,8 +860,8 @@ void deep_fc_fwd(at::Tensor flat, at::Tensor fw, at::Tensor fb,
                 correct_accum.numel() ? correct_accum.data_ptr<int>()
                                       : nullptr,
                 (int)B, (int)FCIN, (int)NCLS, (int)mode,
-                dflat.numel() ? dflat.data_ptr() : nullptr, act_flag(flat),
-                (void*)stream),
+                dflat.numel() ? dflat.data_ptr() : nullptr, ls_ptr(ls_state),
+                act_flag(flat), (void*)stream),
             "deep_fc_fwd");
 }
 
@@ -870,8 +886,9 @@ void deep_fc_wgrad(at::Tensor dz, at::Tensor flat, at::Tensor gfw,
 }
 
 void deep_update(at::Tensor params, at::Tensor grads, double step,
-                 int64_t stream) {
-  const pcnn_opt opt = plain_opt(step);
+                 int64_t stream, c10::optional<at::Tensor> ls_state) {
+  pcnn_opt opt = plain_opt(step);
+  opt.ls_state = ls_ptr(ls_state);
   check_hip(pcnn_deep_update(params.data_ptr<float>(),
                              grads.data_ptr<float>(), params.numel(), &opt,
                              (void*)stream),
@@ -880,9 +897,11 @@ void deep_update(at::Tensor params, at::Tensor grads, double step,
 
 void deep_update_momentum(at::Tensor params, at::Tensor grads,
                           at::Tensor vel, double dt, double scale, double mu,
-                          double wd, bool nesterov, int64_t stream) {
+                          double wd, bool nesterov, int64_t stream,
+                          c10::optional<at::Tensor> ls_state) {
   TORCH_CHECK(grads.numel() == params.numel(), "grads/params size mismatch");
-  const pcnn_opt opt = momentum_opt(vel, params, dt, scale, mu, wd, nesterov);
+  pcnn_opt opt = momentum_opt(vel, params, dt, scale, mu, wd, nesterov);
+  opt.ls_state = ls_ptr(ls_state);
   check_hip(pcnn_deep_update(params.data_ptr<float>(),
                              grads.data_ptr<float>(), params.numel(), &opt,
                              (void*)stream),
@@ -892,14 +911,67 @@ void deep_update_momentum(at::Tensor params, at::Tensor grads,
 void deep_update_adam(at::Tensor params, at::Tensor grads, at::Tensor m,
                       at::Tensor sq, double dt, double scale, double beta1,
                       double beta2, double eps, double wd, int64_t t,
-                      int64_t stream) {
+                      int64_t stream, c10::optional<at::Tensor> ls_state) {
   TORCH_CHECK(grads.numel() == params.numel(), "grads/params size mismatch");
-  const pcnn_opt opt =
-      adam_opt(m, sq, params, dt, scale, beta1, beta2, eps, wd, t);
+  pcnn_opt opt = adam_opt(m, sq, params, dt, scale, beta1, beta2, eps, wd, t);
+  opt.ls_state = ls_ptr(ls_state);
   check_hip(pcnn_deep_update(params.data_ptr<float>(),
                              grads.data_ptr<float>(), params.numel(), &opt,
                              (void*)stream),
             "deep_update_adam");
+}
+
+// Overflow check of a flat fp32 gradient bucket into the scaler state.
+void deep_ls_check(at::Tensor grads, at::Tensor ls_state, int64_t stream) {
+  TORCH_CHECK(grads.is_cuda() && grads.scalar_type() == at::kFloat &&
+                  grads.is_contiguous() && grads.numel() >= 1,
+              "grads must be a contiguous device fp32 tensor");
+  check_hip(pcnn_deep_ls_check(grads.data_ptr<float>(), grads.numel(),
+                               const_cast<float*>(ls_ptr(ls_state)),
+                               (void*)stream),
+            "deep_ls_check");
+}
+
+// The scaler's step after an update (k_ls_advance).
+void deep_ls_advance(at::Tensor ls_state, int64_t growth_interval,
+                     bool dynamic, double beta1, double beta2,
+                     int64_t stream) {
+  check_hip(pcnn_deep_ls_advance(const_cast<float*>(ls_ptr(ls_state)),
+                                 (int)growth_interval, dynamic ? 1 : 0, beta1,
+                                 beta2, (void*)stream),
+            "deep_ls_advance");
+}
+
+// Scaler state from host values: found_inf starts clear, inv_scale is formed
+// here.  c1, c2 belong to update t (tools/deep_emul.py: adam_corrections).
+void deep_ls_init(at::Tensor ls_state, double scale, int64_t good_steps,
+                  int64_t skipped, int64_t t, double c1, double c2) {
+  TORCH_CHECK(ls_ptr(ls_state) != nullptr, "ls_state must not be empty");
+  TORCH_CHECK(scale >= 1.0 && t >= 1 && good_steps >= 0 && skipped >= 0,
+              "deep_ls_init: scale >= 1, t >= 1, counters >= 0");
+  at::Tensor host = at::empty({PCNN_LS_WORDS}, at::kFloat);
+  float* f = host.data_ptr<float>();
+  int32_t* w = reinterpret_cast<int32_t*>(f);
+  f[0] = (float)scale;
+  f[1] = 1.0f / (float)scale;
+  w[2] = 0;
+  w[3] = (int32_t)good_steps;
+  w[4] = (int32_t)skipped;
+  w[5] = (int32_t)t;
+  f[6] = (float)c1;
+  f[7] = (float)c2;
+  ls_state.copy_(host);
+}
+
+// (scale, inv_scale, found_inf, good_steps, skipped, t, c1, c2); waits for
+// the device like any .item().
+py::tuple deep_ls_read(at::Tensor ls_state) {
+  TORCH_CHECK(ls_ptr(ls_state) != nullptr, "ls_state must not be empty");
+  at::Tensor host = ls_state.cpu().contiguous();
+  const float* f = host.data_ptr<float>();
+  const int32_t* w = reinterpret_cast<const int32_t*>(f);
+  return py::make_tuple((double)f[0], (double)f[1], (int)w[2], (int)w[3],
+                        (int)w[4], (int)w[5], (double)f[6], (double)f[7]);
 }
 
 void deep_mfma_selftest(at::Tensor A, at::Tensor Bm, at::Tensor D,
@@ -1035,7 +1107,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("deep_cast_wt", &deep_cast_wt);
   m.def("deep_cast_all", &deep_cast_all);
   m.def("deep_pad_channels", &deep_pad_channels);
-  m.def("deep_update_cast", &deep_update_cast);
+  m.def("deep_update_cast", &deep_update_cast, py::arg("params"),
+        py::arg("grads"), py::arg("step"), py::arg("wbuf"), py::arg("R"), py::arg("C"), py::arg("K"),
+        py::arg("Cin"), py::arg("w_off"), py::arg("bf_off"),
+        py::arg("bfT_off"), py::arg("rot_off"), py::arg("p8_off"),
+        py::arg("stream"), py::arg("ls_state") = py::none());
   m.def("deep_wgrad_multi", &deep_wgrad_multi);
   m.def("deep_remap_dw8", &deep_remap_dw8);
   m.def("deep_wgrad_gemm", &deep_wgrad_gemm, py::arg("cols"),
@@ -1055,14 +1131,41 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("fb"), py::arg("labels"), py::arg("y"), py::arg("dz"),
         py::arg("loss_accum"), py::arg("correct_accum"), py::arg("B"),
         py::arg("FCIN"), py::arg("NCLS"), py::arg("mode"),
-        py::arg("stream"), py::arg("dflat") = at::empty({0}));
+        py::arg("stream"), py::arg("dflat") = at::empty({0}),
+        py::arg("ls_state") = py::none());
   m.def("deep_fc_bwd", &deep_fc_bwd);
   m.def("deep_fc_wgrad", &deep_fc_wgrad);
-  m.def("deep_update", &deep_update);
-  m.def("deep_update_momentum", &deep_update_momentum);
-  m.def("deep_update_cast_momentum", &deep_update_cast_momentum);
-  m.def("deep_update_adam", &deep_update_adam);
-  m.def("deep_update_cast_adam", &deep_update_cast_adam);
+  m.def("deep_update", &deep_update, py::arg("params"), py::arg("grads"),
+        py::arg("step"), py::arg("stream"),
+        py::arg("ls_state") = py::none());
+  m.def("deep_update_momentum", &deep_update_momentum, py::arg("params"),
+        py::arg("grads"), py::arg("vel"), py::arg("dt"), py::arg("scale"),
+        py::arg("mu"), py::arg("wd"), py::arg("nesterov"), py::arg("stream"),
+        py::arg("ls_state") = py::none());
+  m.def("deep_update_cast_momentum", &deep_update_cast_momentum,
+        py::arg("params"), py::arg("grads"), py::arg("vel"), py::arg("dt"),
+        py::arg("scale"), py::arg("mu"), py::arg("wd"), py::arg("nesterov"),
+        py::arg("wbuf"), py::arg("R"), py::arg("C"), py::arg("K"),
+        py::arg("Cin"), py::arg("w_off"), py::arg("bf_off"),
+        py::arg("bfT_off"), py::arg("rot_off"), py::arg("p8_off"),
+        py::arg("stream"), py::arg("ls_state") = py::none());
+  m.def("deep_update_adam", &deep_update_adam, py::arg("params"),
+        py::arg("grads"), py::arg("m"), py::arg("sq"), py::arg("dt"),
+        py::arg("scale"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+        py::arg("wd"), py::arg("t"), py::arg("stream"),
+        py::arg("ls_state") = py::none());
+  m.def("deep_update_cast_adam", &deep_update_cast_adam, py::arg("params"),
+        py::arg("grads"), py::arg("m"), py::arg("sq"), py::arg("dt"),
+        py::arg("scale"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+        py::arg("wd"), py::arg("t"), py::arg("wbuf"), py::arg("R"), py::arg("C"), py::arg("K"),
+        py::arg("Cin"), py::arg("w_off"), py::arg("bf_off"),
+        py::arg("bfT_off"), py::arg("rot_off"), py::arg("p8_off"),
+        py::arg("stream"), py::arg("ls_state") = py::none());
+  m.def("deep_ls_check", &deep_ls_check);
+  m.def("deep_ls_advance", &deep_ls_advance);
+  m.def("deep_ls_init", &deep_ls_init);
+  m.def("deep_ls_read", &deep_ls_read);
+  m.attr("LS_WORDS") = PCNN_LS_WORDS;
   m.def("deep_mfma_selftest", &deep_mfma_selftest);
   m.attr("N_PARAMS") = pcnn::N_PARAMS;
   m.attr("GSLAB_LD") = pcnn::GSLAB_LD;

@@ -1532,13 +1532,18 @@ __global__ __launch_bounds__(256) void k_pool_wbwd8(
 // the block's dz is in LDS, the same block computes dflat[b][m] =
 // (sum_k fw[k][m] dz[k]) * flat*(1-flat) for its sample (kills the
 // separate k_fc_bwd launch; fw re-read comes from L2).
+// ls != null (loss scaling): the residual is multiplied by the scaler's
+// `scale` where it starts the backward pass -- dzs (the fused dflat) and dzg
+// (k_fc_wgrad, k_fc_bwd) -- so every gradient stored in activation dtype and
+// the whole bucket come out scale x larger.  The loss and yg stay unscaled.
 template <typename act_t>
 __global__ __launch_bounds__(256) void k_fc_fwd(
     const act_t* __restrict__ flat, const float* __restrict__ fw,
     const float* __restrict__ fb, const int* __restrict__ labels,
     float* __restrict__ yg, float* __restrict__ dzg,
     float* __restrict__ loss_accum, int* __restrict__ correct_accum, int B,
-    int FCIN, int NCLS, int mode, act_t* __restrict__ dflat) {
+    int FCIN, int NCLS, int mode, act_t* __restrict__ dflat,
+    const float* __restrict__ ls) {
   __shared__ float ys[32];
   __shared__ float sq[32];
   __shared__ float dzs[32];
@@ -1574,8 +1579,9 @@ __global__ __launch_bounds__(256) void k_fc_fwd(
       if (mode == 0) {
         const float d = (k == labels[b] ? 1.0f : 0.0f) - v;
         sq[k] = d * d;
-        dzs[k] = d;
-        dzg[(long long)b * NCLS + k] = d;
+        const float ds = ls != nullptr ? d * ls[LS_SCALE] : d;
+        dzs[k] = ds;
+        dzg[(long long)b * NCLS + k] = ds;
       }
     }
   }
@@ -2035,6 +2041,151 @@ __global__ void k_update_n_adam(float* __restrict__ params,
   update_n_body<OPT_ADAM>(params, grads, vel, sq, n, 0.f, o);
 }
 
+// ---------------------------------------------------------------------------
+// Loss scaling (pcnn_launch.h, sgd_update.h: LS_* word indices).
+// ---------------------------------------------------------------------------
+// The update kernels with a scaler state, one template per site for all three
+// optimizers.  found_inf set: the step is skipped -- the gradient bucket is
+// zeroed and params, vel, sq and the bf16 images keep their bits.  Clear: the
+// update of sgd_apply1 with the step (plain) or scale (momentum, Adam)
+// multiplied by inv_scale and Adam's c1, c2 read from the state (ls_args).
+// The unscaled kernels above are left as they are: an extra pointer argument
+// or a template over them moves their register allocation.
+template <int OPT, typename Args>
+__global__ void k_update_n_ls(float* __restrict__ params,
+                              float* __restrict__ grads,
+                              float* __restrict__ vel, float* __restrict__ sq,
+                              long long n, float step, Args o,
+                              const float* __restrict__ ls) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (ls_found_inf(ls)) {
+    grads[i] = 0.f;
+    return;
+  }
+  if constexpr (OPT == OPT_PLAIN)
+    sgd_apply1<OPT>(params, grads, vel, sq, i, ls_step(step, ls), o);
+  else
+    sgd_apply1<OPT>(params, grads, vel, sq, i, 0.f, ls_args(o, ls));
+}
+
+template <int OPT, typename Args>
+__global__ void k_update_cast_all_ls(float* __restrict__ params,
+                                     float* __restrict__ grads,
+                                     float* __restrict__ vel,
+                                     float* __restrict__ sq, long long n,
+                                     float step, Args o,
+                                     const float* __restrict__ ls,
+                                     __bf16* __restrict__ wbuf, CastDescs d) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (ls_found_inf(ls)) {
+    grads[i] = 0.f;
+    return;
+  }
+  float pnew;
+  if constexpr (OPT == OPT_PLAIN)
+    pnew = sgd_apply1<OPT>(params, grads, vel, sq, i, ls_step(step, ls), o);
+  else
+    pnew = sgd_apply1<OPT>(params, grads, vel, sq, i, 0.f, ls_args(o, ls));
+  for (int s = 0; s < d.n; ++s) {
+    const long long q = i - d.w_off[s];
+    if (q < 0 || q >= d.cum[s + 1] - d.cum[s]) continue;
+    const int C = d.C[s];
+    const int kc = (int)(q / C);
+    const int c = (int)(q - (long long)kc * C);
+    const __bf16 v = (__bf16)pnew;
+    wbuf[d.bf_off[s] + q] = v;
+    wbuf[d.bfT_off[s] + (long long)c * d.R[s] + kc] = v;
+    const int Cin = d.Cin[s], K = d.K[s];
+    if (kc < K * K * Cin) {
+      const int ci = kc % Cin;
+      const int p2 = kc / Cin;
+      const int ki = p2 / K, kj = p2 - ki * K;
+      const int col = ((K - 1 - ki) * K + (K - 1 - kj)) * C + c;
+      wbuf[d.rot_off[s] + (long long)ci * (K * K * C) + col] = v;
+      if (d.p8_off[s] >= 0)
+        wbuf[d.p8_off[s] + (long long)c * (K * K * 8) + p2 * 8 + ci] = v;
+    }
+    break;
+  }
+}
+
+// Overflow check of the flat gradient bucket: n4 float4 vectors grid-strided,
+// then the n - 4*n4 tail elements.  A value is inf or NaN exactly when its
+// exponent bits are all ones.  Each wave votes; a wave that saw one stores 1
+// to found_inf from one lane.  Every writer stores the same value, so the
+// stores need no ordering among themselves, and nothing here ever stores 0:
+// a flag that was set stays set.
+__device__ __forceinline__ bool ls_nonfinite(float v) {
+  return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;
+}
+
+__global__ __launch_bounds__(256) void k_ls_check(
+    const float* __restrict__ grads, long long n, float* __restrict__ ls) {
+  const long long n4 = n >> 2;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  bool bad = false;
+  for (long long i = i0; i < n4; i += stride) {
+    const float4 g = reinterpret_cast<const float4*>(grads)[i];
+    bad = bad || ls_nonfinite(g.x) || ls_nonfinite(g.y) ||
+          ls_nonfinite(g.z) || ls_nonfinite(g.w);
+  }
+  const long long it = 4 * n4 + i0;   // the tail: at most 3 elements
+  if (it < n) bad = bad || ls_nonfinite(grads[it]);
+  if (__any(bad) && (threadIdx.x & 63) == 0)
+    reinterpret_cast<int*>(ls)[LS_FOUND_INF] = 1;
+}
+
+// beta^t for an integer t >= 0 by repeated squaring, IEEE double products
+// only: the Python reference (advance_reference, tools/deep_emul.py) runs the
+// same products in the same order and lands on the same bits, which a
+// library pow on either side would not promise.
+__device__ __forceinline__ double ls_ipow(double b, int t) {
+#pragma clang fp contract(off)
+  double r = 1.0;
+  while (t > 0) {
+    if (t & 1) r = r * b;
+    b = b * b;
+    t >>= 1;
+  }
+  return r;
+}
+
+// The scaler's step, one thread, after the update (pcnn_launch.h).
+__global__ void k_ls_advance(float* __restrict__ ls, int growth_interval,
+                             int dynamic, double beta1, double beta2) {
+#pragma clang fp contract(off)   // 1 - beta^t must not fuse into an fma
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  int* li = reinterpret_cast<int*>(ls);
+  float scale = ls[LS_SCALE];
+  int good = li[LS_GOOD_STEPS];
+  if (li[LS_FOUND_INF] != 0) {
+    li[LS_SKIPPED] += 1;
+    if (dynamic) {
+      scale = fmaxf(0.5f * scale, 1.0f);
+      good = 0;
+    }
+  } else {
+    const int t = li[LS_T] + 1;
+    li[LS_T] = t;
+    ls[LS_C1] = (float)(1.0 / (1.0 - ls_ipow(beta1, t)));
+    ls[LS_C2] = (float)(1.0 / sqrt(1.0 - ls_ipow(beta2, t)));
+    if (dynamic) {
+      good += 1;
+      if (good >= growth_interval) {
+        scale = fminf(2.0f * scale, 16777216.0f);
+        good = 0;
+      }
+    }
+  }
+  ls[LS_SCALE] = scale;
+  ls[LS_INV_SCALE] = 1.0f / scale;   // exact: scale is a power of two
+  li[LS_GOOD_STEPS] = good;
+  li[LS_FOUND_INF] = 0;
+}
+
 // MFMA layout self-test: D[16][16] = A[16][32] @ B[32][16], plain fp32 I/O.
 __global__ void k_mfma_selftest(const float* __restrict__ A,
                                 const float* __restrict__ Bm,
@@ -2219,6 +2370,25 @@ int pcnn_deep_update_cast(float* params, float* grads, long long n,
   dim3 grid((unsigned)((n + 255) / 256)), block(256);
   const int sel = opt_select(opt);
   if (sel < 0) return -2;
+  if (opt->ls_state != nullptr) {
+    hipStream_t st = (hipStream_t)stream;
+    const float* ls = opt->ls_state;
+    if (sel == OPT_ADAM)
+      hipLaunchKernelGGL((k_update_cast_all_ls<OPT_ADAM, AdamArgs>), grid,
+                         block, 0, st, params, grads, opt->vel, opt->sq, n,
+                         0.f, adam_args(opt), ls, (__bf16*)wbuf, d);
+    else if (sel == OPT_MOM)
+      hipLaunchKernelGGL((k_update_cast_all_ls<OPT_MOM, MomArgs>), grid,
+                         block, 0, st, params, grads, opt->vel,
+                         (float*)nullptr, n, 0.f, mom_args(opt), ls,
+                         (__bf16*)wbuf, d);
+    else
+      hipLaunchKernelGGL((k_update_cast_all_ls<OPT_PLAIN, MomArgs>), grid,
+                         block, 0, st, params, grads, (float*)nullptr,
+                         (float*)nullptr, n, opt->step, MomArgs{}, ls,
+                         (__bf16*)wbuf, d);
+    return (int)hipGetLastError();
+  }
   if (sel == OPT_ADAM)
     hipLaunchKernelGGL(k_update_cast_all_adam, grid, block, 0,
                        (hipStream_t)stream, params, grads, opt->vel, opt->sq,
@@ -2438,15 +2608,15 @@ int pcnn_deep_pool_wbwd(const void* dppre, const void* a, const float* pw,
 int pcnn_deep_fc_fwd(const void* flat, const float* fw, const float* fb,
                       const int* labels, float* yg, float* dzg,
                       float* loss_accum, int* correct_accum, int B, int FCIN,
-                      int NCLS, int mode, void* dflat, int actf,
-                      void* stream) {
+                      int NCLS, int mode, void* dflat, const float* ls_state,
+                      int actf, void* stream) {
   dim3 grid(B), block(256);
   PCNN_DISPATCH(actf, hipLaunchKernelGGL((k_fc_fwd<act_t>), grid, block, 0,
                                           (hipStream_t)stream,
                                           (const act_t*)flat, fw, fb, labels,
                                           yg, dzg, loss_accum, correct_accum,
                                           B, FCIN, NCLS, mode,
-                                          (act_t*)dflat));
+                                          (act_t*)dflat, ls_state));
   return (int)hipGetLastError();
 }
 
@@ -2481,6 +2651,23 @@ int pcnn_deep_update(float* params, float* grads, long long n,
   dim3 grid((unsigned)((n + 255) / 256)), block(256);
   const int sel = opt_select(opt);
   if (sel < 0) return -2;
+  if (opt->ls_state != nullptr) {
+    hipStream_t st = (hipStream_t)stream;
+    const float* ls = opt->ls_state;
+    if (sel == OPT_ADAM)
+      hipLaunchKernelGGL((k_update_n_ls<OPT_ADAM, AdamArgs>), grid, block, 0,
+                         st, params, grads, opt->vel, opt->sq, n, 0.f,
+                         adam_args(opt), ls);
+    else if (sel == OPT_MOM)
+      hipLaunchKernelGGL((k_update_n_ls<OPT_MOM, MomArgs>), grid, block, 0,
+                         st, params, grads, opt->vel, (float*)nullptr, n, 0.f,
+                         mom_args(opt), ls);
+    else
+      hipLaunchKernelGGL((k_update_n_ls<OPT_PLAIN, MomArgs>), grid, block, 0,
+                         st, params, grads, (float*)nullptr, (float*)nullptr,
+                         n, opt->step, MomArgs{}, ls);
+    return (int)hipGetLastError();
+  }
   if (sel == OPT_ADAM)
     hipLaunchKernelGGL(k_update_n_adam, grid, block, 0, (hipStream_t)stream,
                        params, grads, opt->vel, opt->sq, n, adam_args(opt));
@@ -2490,6 +2677,31 @@ int pcnn_deep_update(float* params, float* grads, long long n,
   else
     hipLaunchKernelGGL(k_update_n, grid, block, 0, (hipStream_t)stream,
                        params, grads, n, opt->step);
+  return (int)hipGetLastError();
+}
+
+int pcnn_deep_ls_check(const float* grads, long long n, float* ls_state,
+                       void* stream) {
+  if (grads == nullptr || ls_state == nullptr || n < 1 ||
+      ((uintptr_t)grads & 15) != 0)
+    return -2;
+  // up to 1024 blocks of 256 lanes, each lane one float4 per trip; the
+  // one-element tail needs at least one block
+  long long blocks = ((n >> 2) + 255) / 256;
+  if (blocks < 1) blocks = 1;
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(k_ls_check, dim3((unsigned)blocks), dim3(256), 0,
+                     (hipStream_t)stream, grads, n, ls_state);
+  return (int)hipGetLastError();
+}
+
+int pcnn_deep_ls_advance(float* ls_state, int growth_interval, int dynamic,
+                         double beta1, double beta2, void* stream) {
+  if (ls_state == nullptr || growth_interval < 1 || !(beta1 >= 0.0) ||
+      !(beta1 < 1.0) || !(beta2 >= 0.0) || !(beta2 < 1.0))
+    return -2;
+  hipLaunchKernelGGL(k_ls_advance, dim3(1), dim3(64), 0, (hipStream_t)stream,
+                     ls_state, growth_interval, dynamic, beta1, beta2);
   return (int)hipGetLastError();
 }
 

@@ -1578,6 +1578,11 @@ __global__ __launch_bounds__(256) void k_reduce_update_adam(
 // (opt_select, sgd_update.h).
 // ---------------------------------------------------------------------------
 
+// Loss scaling is a DeepCNN feature: this family's in-block step never
+// stores a gradient in activation dtype.  Every launcher that takes an
+// optimizer refuses a scaler state (pcnn_opt.ls_state) with this code.
+enum { LS_REFUSED = -3 };
+
 using namespace pcnn;
 
 namespace {
@@ -1619,6 +1624,7 @@ int launch_wgrad_any(const void* x, const void* a1, const void* a2,
   if (FS < 1) FS = 1;
   if (FS > 32) FS = 32;
   dim3 grid(C1_CH * GC + GS + FS * FC_BLOCKS), block(256);
+  if (ticket != nullptr && opt->ls_state != nullptr) return LS_REFUSED;
   const int sel = ticket == nullptr ? OPT_PLAIN : opt_select(opt);
   if (sel < 0) return (int)hipErrorInvalidValue;
   PCNN_DISPATCH(act, {
@@ -1683,6 +1689,7 @@ int pcnn_launch_wgrad(const void* x, const void* a1, const void* a2,
 int pcnn_launch_update(float* params, float* grads, const pcnn_opt* opt,
                        void* stream) {
   if (opt == nullptr) return (int)hipErrorInvalidValue;
+  if (opt->ls_state != nullptr) return LS_REFUSED;
   dim3 grid((N_PARAMS / 4 + 255) / 256), block(256);
   const int sel = opt_select(opt);
   if (sel < 0) return (int)hipErrorInvalidValue;
@@ -1766,6 +1773,7 @@ int pcnn_launch_reduce_update(const float* gslab, const void* a2,
                               void* stream) {
   if (gslab == nullptr || params == nullptr || opt == nullptr || B < 1)
     return (int)hipErrorInvalidValue;
+  if (opt->ls_state != nullptr) return LS_REFUSED;
   dim3 grid(RU_BLOCKS), block(256);
   hipStream_t s = (hipStream_t)stream;
   const int sel = opt_select(opt);
@@ -1802,6 +1810,8 @@ int pcnn_launch_step_inblock(const void* x, float* params, void* a1, void* a2,
                              const pcnn_opt* opt, int B, int act,
                              int pool_mode, int loss_mode, int chunk_imgs,
                              int variant, void* stream) {
+  // refused before the forward/backward launch, not after it
+  if (opt != nullptr && opt->ls_state != nullptr) return LS_REFUSED;
   // k_reduce_update walks the batch with 4 lanes per parameter, so its cost
   // grows linearly with B while k_wgrad_update spreads a larger batch over
   // more blocks.  Measured (MI355X, bf16, us/step, in-block vs

@@ -60,6 +60,53 @@ inline int opt_select(const pcnn_opt* opt) {
   return opt->vel != nullptr ? OPT_MOM : OPT_PLAIN;
 }
 
+// Loss scaling (DeepCNN only): the device-resident scaler state, eight
+// 32-bit words behind pcnn_opt.ls_state.  scale, inv_scale, c1 and c2 are
+// floats; found_inf, good_steps, skipped and t are int32 stored in place.
+// t is the 1-based count of the update that c1, c2 belong to, the next one
+// to be applied: t - 1 updates have been applied so far.
+enum {
+  LS_SCALE = 0,
+  LS_INV_SCALE = 1,
+  LS_FOUND_INF = 2,
+  LS_GOOD_STEPS = 3,
+  LS_SKIPPED = 4,
+  LS_T = 5,
+  LS_C1 = 6,
+  LS_C2 = 7,
+  LS_WORDS = 8
+};
+
+// LS is the fourth compile-time selector of an update site: false leaves
+// the step and the argument struct as the launcher passed them.  true reads
+// the state: the gradients in the bucket are scale x the true ones, so the
+// plain step and the `scale` of the momentum and Adam forms are multiplied
+// by inv_scale, and Adam takes c1, c2 from the state (its update count lives
+// there, not on the host).  The update body itself is sgd_apply1/4 above all
+// the same.
+__device__ __forceinline__ bool ls_found_inf(const float* __restrict__ ls) {
+  return reinterpret_cast<const int*>(ls)[LS_FOUND_INF] != 0;
+}
+
+__device__ __forceinline__ float ls_step(float step,
+                                         const float* __restrict__ ls) {
+  return step * ls[LS_INV_SCALE];
+}
+
+__device__ __forceinline__ MomArgs ls_args(MomArgs o,
+                                           const float* __restrict__ ls) {
+  o.scale *= ls[LS_INV_SCALE];
+  return o;
+}
+
+__device__ __forceinline__ AdamArgs ls_args(AdamArgs o,
+                                            const float* __restrict__ ls) {
+  o.scale *= ls[LS_INV_SCALE];
+  o.c1 = ls[LS_C1];
+  o.c2 = ls[LS_C2];
+  return o;
+}
+
 __device__ __forceinline__ float mom_apply(float p, float g, float& v,
                                            const MomArgs& o) {
   const float u = o.scale * g - o.wd * p;

@@ -32,7 +32,18 @@ extern "C" {
  * c2 = 1/sqrt(1-beta2^t) for the 1-based update count t, and omb1 = 1-beta1,
  * omb2 = 1-beta2 (1.f - beta2 in float would carry beta2's own rounding).
  * `step` and `nesterov` are ignored.  The fields from `kind` on were
- * appended: an initialiser that stops at vel leaves them zero, kind 0. */
+ * appended: an initialiser that stops at vel leaves them zero, kind 0.
+ *
+ * ls_state (appended last; NULL = everything above, unchanged): the loss
+ * scaler's device state, PCNN_LS_WORDS 32-bit words laid out as float scale,
+ * float inv_scale, int32 found_inf, int32 good_steps, int32 skipped, int32 t,
+ * float c1, float c2.  The bucket then holds scale x the gradients.  With
+ * found_inf set the update kernels zero the gradient bucket and touch
+ * nothing else; with it clear they apply the update with `step` (plain) or
+ * `scale` (momentum, Adam) multiplied by inv_scale, and Adam reads c1, c2
+ * from the state instead of from this struct.  DeepCNN launchers only: the
+ * LeNet launchers refuse a non-NULL ls_state with -3. */
+#define PCNN_LS_WORDS 8
 typedef struct pcnn_opt {
   float step;
   float scale, dt, mu, wd;
@@ -42,6 +53,7 @@ typedef struct pcnn_opt {
   float* sq;
   float beta2, eps, c1, c2;
   float omb1, omb2;
+  const float* ls_state;
 } pcnn_opt;
 
 const char* pcnn_hip_error_string(int err);
@@ -148,13 +160,26 @@ int pcnn_deep_pool_wbwd(const void* dppre, const void* a, const float* pw,
 int pcnn_deep_fc_fwd(const void* flat, const float* fw, const float* fb,
                      const int* labels, float* yg, float* dzg,
                      float* loss_accum, int* correct_accum, int B, int FCIN,
-                     int NCLS, int mode, void* dflat, int act, void* stream);
+                     int NCLS, int mode, void* dflat, const float* ls_state,
+                     int act, void* stream);
 int pcnn_deep_fc_bwd(const float* dzg, const void* flat, const float* fw,
                      void* dflat, int B, int FCIN, int NCLS, int act,
                      void* stream);
 int pcnn_deep_fc_wgrad(const float* dzg, const void* flat, float* gfw,
                        float* gfb, int B, int FCIN, int NCLS, int FS, int act,
                        void* stream);
+/* Loss scaling.  ls_check: one pass over the flat gradient bucket (16-byte
+ * aligned); any inf or NaN sets found_inf, nothing ever clears it here.
+ * ls_advance: one thread, after the update.  found_inf set: scale =
+ * max(scale/2, 1), good_steps = 0, skipped += 1, t and c1, c2 stay.  Clear:
+ * t += 1, c1 = 1/(1-beta1^t), c2 = 1/sqrt(1-beta2^t) in double, good_steps
+ * += 1 and, on reaching growth_interval, scale = min(2*scale, 2^24) and
+ * good_steps = 0.  dynamic == 0 (a fixed scale) leaves scale and good_steps
+ * alone; skips are still counted.  found_inf is cleared at the end. */
+int pcnn_deep_ls_check(const float* grads, long long n, float* ls_state,
+                       void* stream);
+int pcnn_deep_ls_advance(float* ls_state, int growth_interval, int dynamic,
+                         double beta1, double beta2, void* stream);
 int pcnn_deep_mfma_selftest(const float* A, const float* Bm, float* D,
                             void* stream);
 

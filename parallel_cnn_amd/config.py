@@ -7,10 +7,14 @@ from __future__ import annotations
 
 import argparse
 import dataclasses
+import math
 from dataclasses import dataclass, field
 from typing import Optional
 
 from .ops.shapes import REF_DT, REF_THRESHOLD
+
+
+LOSS_SCALE_MAX = 16777216.0      # 2^24, the scaler's upper clamp (1 below)
 
 
 @dataclass
@@ -43,6 +47,55 @@ class TrainConfig:
     beta1: float = 0.9
     beta2: float = 0.999
     adam_eps: float = 1e-8
+
+    # fp16 loss scaling, DeepCNN hip path only: off | dynamic | a fixed
+    # power of two in [1, 2^24].  The backward pass starts from scale x the
+    # residual, so the gradients stored in activation dtype (fp16's smallest
+    # subnormal is 6e-8) stay representable; the update divides by scale
+    # again and skips a step whose gradient bucket holds an inf or NaN.
+    # dynamic starts at loss_scale_init, halves on a skipped step and
+    # doubles after loss_scale_growth_interval applied updates in a row
+    # (factors 2 and 0.5, clamp [1, 2^24]).  The scaler lives on the device;
+    # the host never reads it during a step.
+    loss_scale: str = "off"
+    loss_scale_init: float = 65536.0
+    loss_scale_growth_interval: int = 2000
+
+    def __post_init__(self):
+        # YAML reads `loss_scale: 8192` as a number; the field is a string
+        self.loss_scale = str(self.loss_scale)
+
+    def loss_scaling(self):
+        """None when loss scaling is off, else (initial scale, dynamic);
+        validates the three loss_scale fields (ValueError).  On the cpu and
+        torchref backends the key is accepted and has no numeric effect:
+        their storage is fp32 and nothing underflows.  LeNet refuses it: its
+        in-block step never stores a gradient in activation dtype."""
+        def pow2(v, what):
+            try:
+                f = float(v)
+            except (TypeError, ValueError):
+                f = 0.0
+            m, _ = math.frexp(f)
+            if not (1.0 <= f <= LOSS_SCALE_MAX and m == 0.5):
+                raise ValueError(
+                    f"{what} must be a power of two in [1, 2^24], got {v!r}")
+            return f
+        if int(self.loss_scale_growth_interval) < 1:
+            raise ValueError(
+                f"loss_scale_growth_interval must be >= 1, got "
+                f"{self.loss_scale_growth_interval}")
+        init = pow2(self.loss_scale_init, "loss_scale_init")
+        mode = str(self.loss_scale).strip().lower()
+        if mode == "off":
+            return None
+        if self.model == "lenet5":
+            raise ValueError(
+                "loss_scale is a DeepCNN option; model lenet5 never stores "
+                "gradients in activation dtype")
+        if mode == "dynamic":
+            return init, True
+        return pow2(mode, "loss_scale (off, dynamic or a number)"), False
 
     def uses_adam(self) -> bool:
         """True when the optimizer is Adam (first- and second-moment

@@ -15,6 +15,13 @@ launch with the bias colsums folded in}; one fused DP all-reduce of the
 flat gradient bucket; SGD (or momentum, or Adam) update fused with the next
 step's weight cast.
 deep_implicit=False keeps the round-1 materialized-cols path.
+
+Loss scaling (cfg.loss_scale != off, hip only) adds two launches around the
+update: the fc forward starts the backward pass from scale x the residual,
+k_ls_check looks for an inf or NaN in the all-reduced bucket, the update
+kernels divide by the scale or skip the step, and k_ls_advance moves the
+scaler.  The scaler (and with it the count of applied updates) lives in one
+device buffer, ls_state; the host reads it only in loss_scale_state().
 """
 from __future__ import annotations
 
@@ -24,7 +31,7 @@ import torch
 
 from ..config import TrainConfig
 from ..models.deepcnn import DeepCNN
-from ..ops import deep_ref, native, torch_ref
+from ..ops import deep_ref, loss_scale_ref, native, torch_ref
 from ..parallel import dist as pdist
 
 MODE_TRAIN, MODE_EVAL, MODE_INFER = 0, 1, 2
@@ -222,7 +229,18 @@ class DeepTrainer:
         if cfg.uses_adam():
             self.vel = torch.zeros_like(self.model.params)
             self.sq = torch.zeros_like(self.model.params)
-        self.opt_step = 0
+        self._opt_step = 0
+        # loss scaler: one device buffer of LS_WORDS words (hip only; the
+        # torchref path stores fp32 and has nothing to rescue).  None = off:
+        # no buffer, no extra launch, the unscaled kernels.
+        self.ls_state: Optional[torch.Tensor] = None
+        ls = cfg.loss_scaling()
+        if ls is not None and backend == "hip":
+            self._ls_dynamic = ls[1]
+            self.ls_state = torch.zeros(self._C.LS_WORDS,
+                                        dtype=torch.float32,
+                                        device=self.device)
+            self.set_loss_scale_state(scale=ls[0])
         act_map = {"bf16": torch.bfloat16, "fp16": torch.float16,
                    "fp32": torch.float32}
         self.act_dtype = (act_map[cfg.act_dtype] if backend == "hip"
@@ -243,6 +261,90 @@ class DeepTrainer:
     def enable_profiling(self) -> None:
         from ..utils.timers import PhaseTimers
         self.timers = PhaseTimers()
+
+    # ----------------------------------------------------------- loss scaler
+    def _ls_betas(self) -> Tuple[float, float]:
+        """The betas the scaler forms c1, c2 from; zero (c1 = c2 = 1) when
+        the optimizer is not Adam and nothing reads them."""
+        if self.sq is not None:
+            return float(self.cfg.beta1), float(self.cfg.beta2)
+        return 0.0, 0.0
+
+    def loss_scale_state(self) -> Optional[dict]:
+        """{scale, good_steps, skipped, t} read back from the device, None
+        without loss scaling.  t is the 1-based count of the next update
+        (t - 1 were applied).  A sync point, like consume_loss."""
+        if self.ls_state is None:
+            return None
+        scale, _, _, good, skipped, t, _, _ = self._C.deep_ls_read(
+            self.ls_state)
+        return {"scale": scale, "good_steps": good, "skipped": skipped,
+                "t": t}
+
+    def set_loss_scale_state(self, scale: float, good_steps: int = 0,
+                             skipped: int = 0, t: int = 1) -> None:
+        """(Re)initialise the device scaler: construction, checkpoint
+        load."""
+        b1, b2 = self._ls_betas()
+        c1, c2 = loss_scale_ref.adam_corrections(b1, b2, t)
+        self._C.deep_ls_init(self.ls_state, scale, good_steps, skipped, t,
+                             c1, c2)
+
+    @property
+    def opt_step(self) -> int:
+        """Updates applied so far.  With loss scaling the count lives on
+        the device (a skipped step does not advance it) and reading it
+        waits for the device."""
+        if self.ls_state is not None:
+            return self.loss_scale_state()["t"] - 1
+        return self._opt_step
+
+    @opt_step.setter
+    def opt_step(self, n: int) -> None:
+        self._opt_step = int(n)
+        if self.ls_state is not None:
+            st = self.loss_scale_state()
+            self.set_loss_scale_state(st["scale"], st["good_steps"],
+                                      st["skipped"], int(n) + 1)
+
+    @property
+    def update_launches(self):
+        """The launcher calls of one applied update, in order (the
+        all-reduce, a collective, goes ahead of them)."""
+        upd = ("deep_update_cast_adam" if self.sq is not None else
+               "deep_update_cast_momentum" if self.vel is not None else
+               "deep_update_cast")
+        if self.ls_state is None:
+            return [upd]
+        return ["deep_ls_check", upd, "deep_ls_advance"]
+
+    def _apply_update(self, scale: float) -> None:
+        """All-reduce + update of one optimizer step.  With loss scaling:
+        the overflow check runs AFTER the all-reduce (an inf or NaN on any
+        rank survives the sum, so every rank reaches the same verdict and
+        the per-rank scaler states stay bit-identical), the update kernels
+        read the verdict, and the scaler advances behind them."""
+        tm = self.timers
+        if tm is not None:
+            with tm.phase("all-reduce"):
+                pdist.allreduce_grads(self.model.grads)
+            with tm.phase("update"):
+                self._hip_check_update_advance(scale)
+            return
+        pdist.allreduce_grads(self.model.grads)
+        self._hip_check_update_advance(scale)
+
+    def _hip_check_update_advance(self, scale: float) -> None:
+        if self.ls_state is None:
+            self._hip_update(scale)
+            return
+        st_h = native.current_stream_handle()
+        self._C.deep_ls_check(self.model.grads, self.ls_state, st_h)
+        self._hip_update(scale)
+        b1, b2 = self._ls_betas()
+        self._C.deep_ls_advance(self.ls_state,
+                                int(self.cfg.loss_scale_growth_interval),
+                                self._ls_dynamic, b1, b2, st_h)
 
     # ------------------------------------------------------------------ util
     def _scale(self, B: int) -> float:
@@ -282,31 +384,37 @@ class DeepTrainer:
         self._wbuf_fresh = True
 
     def _hip_update(self, scale: float) -> None:
-        """SGD update fused with the next step's weight cast."""
+        """SGD update fused with the next step's weight cast.  With loss
+        scaling the kernels take the scaler state: they divide by the scale,
+        skip an overflowed step, and Adam's c1, c2 come from the state (the
+        `t` passed here is then a placeholder)."""
         d = self.ws.cast_desc
         c = self.cfg
-        self.opt_step += 1
+        ls = self.ls_state
+        if ls is None:
+            self._opt_step += 1
         if self.sq is not None:
             self._C.deep_update_cast_adam(
                 self.model.params, self.model.grads, self.vel, self.sq, c.dt,
                 scale, c.beta1, c.beta2, c.adam_eps, c.weight_decay,
-                self.opt_step, self.ws.wbuf, d["R"], d["C"], d["K"],
-                d["Cin"], d["w_off"], d["bf_off"], d["bfT_off"],
-                d["rot_off"], d["p8_off"], native.current_stream_handle())
+                self._opt_step if ls is None else 1, self.ws.wbuf, d["R"],
+                d["C"], d["K"], d["Cin"], d["w_off"], d["bf_off"],
+                d["bfT_off"], d["rot_off"], d["p8_off"],
+                native.current_stream_handle(), ls)
         elif self.vel is not None:
             self._C.deep_update_cast_momentum(
                 self.model.params, self.model.grads, self.vel, c.dt, scale,
                 c.momentum, c.weight_decay, c.nesterov, self.ws.wbuf,
                 d["R"], d["C"], d["K"], d["Cin"], d["w_off"], d["bf_off"],
                 d["bfT_off"], d["rot_off"], d["p8_off"],
-                native.current_stream_handle())
+                native.current_stream_handle(), ls)
         else:
             self._C.deep_update_cast(self.model.params, self.model.grads,
                                      self.cfg.dt * scale, self.ws.wbuf,
                                      d["R"], d["C"], d["K"], d["Cin"],
                                      d["w_off"], d["bf_off"], d["bfT_off"],
                                      d["rot_off"], d["p8_off"],
-                                     native.current_stream_handle())
+                                     native.current_stream_handle(), ls)
         self._wbuf_fresh = True
 
     def _hip_forward(self, x: torch.Tensor, labels: torch.Tensor, B: int,
@@ -371,7 +479,9 @@ class DeepTrainer:
                             w.correct_accum, B, spec.fc_in, spec.n_classes,
                             mode, st_h,
                             dflat=w.dppre[-1] if mode == MODE_TRAIN
-                            else torch.empty(0))
+                            else torch.empty(0),
+                            ls_state=self.ls_state if mode == MODE_TRAIN
+                            else None)
 
     def _wgrad_side(self):
         """Lazy side stream + events for the async-wgrad mode: weight
@@ -572,7 +682,9 @@ class DeepTrainer:
         provided for the small-batch regime where Python launch overhead
         binds, and as the capture-compatibility check for the step.
         Same shape as the LeNet trainer's capture: warmup on a side
-        stream with the training state snapshotted/restored.  Not available
+        stream with the training state (the loss scaler's included)
+        snapshotted/restored.  Loss scaling captures as it is: the scaler is
+        device-resident and no kernel argument depends on it.  Not available
         under Adam, whose bias corrections are kernel arguments that change
         with every update."""
         if self.backend != "hip":
@@ -596,7 +708,8 @@ class DeepTrainer:
         params0 = self.model.params.clone()
         grads0 = self.model.grads.clone()
         vel0 = self.vel.clone() if self.vel is not None else None
-        opt_step0 = self.opt_step
+        opt_step0 = self._opt_step
+        ls0 = self.ls_state.clone() if self.ls_state is not None else None
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -611,9 +724,11 @@ class DeepTrainer:
             self.model.grads.copy_(grads0)
             if vel0 is not None:
                 self.vel.copy_(vel0)
+            if ls0 is not None:
+                self.ls_state.copy_(ls0)
             self.ws.loss_accum.zero_()
             self.ws.correct_accum.zero_()
-        self.opt_step = opt_step0
+        self._opt_step = opt_step0
         # the captured graph contains NO cast (warmup left wbuf fresh at
         # capture); refresh it for the restored params before any replay
         self._hip_cast_weights(force=True)
@@ -623,14 +738,15 @@ class DeepTrainer:
         self._hip_forward(self._gx, self._gl, B, MODE_TRAIN)
         self._hip_backward(self._gx, B)
         pdist.allreduce_grads(self.model.grads)
-        self._hip_update(self._scale(B))
+        self._hip_check_update_advance(self._scale(B))
 
     def step_graph(self, x: torch.Tensor, labels: torch.Tensor) -> None:
         """Replay the captured step on a staged batch (two D2D copies)."""
         self._gx.copy_(x.view(self._gx.shape), non_blocking=True)
         self._gl.copy_(labels, non_blocking=True)
         self._graph.replay()
-        self.opt_step += 1
+        if self.ls_state is None:
+            self._opt_step += 1
         self._samples_seen += x.shape[0] * self.ctx.world_size
         self.global_step += 1
 
@@ -654,18 +770,14 @@ class DeepTrainer:
                 with self.timers.phase("backward"):
                     self._hip_backward(x, B)
                 if apply_update:
-                    with self.timers.phase("all-reduce"):
-                        pdist.allreduce_grads(self.model.grads)
-                    with self.timers.phase("update"):
-                        self._hip_update(scale)
+                    self._apply_update(scale)
                 self._samples_seen += B * self.ctx.world_size
                 self.global_step += 1
                 return
             self._hip_forward(x, labels, B, MODE_TRAIN)
             self._hip_backward(x, B)
             if apply_update:
-                pdist.allreduce_grads(self.model.grads)
-                self._hip_update(scale)
+                self._apply_update(scale)
         else:
             spec = self.model.spec
             xh = x.view(B, spec.in_h, spec.in_w, spec.in_ch)
@@ -676,13 +788,13 @@ class DeepTrainer:
             self.model.grads += grads
             if apply_update:
                 pdist.allreduce_grads(self.model.grads)
-                self.opt_step += 1
+                self._opt_step += 1
                 c = self.cfg
                 if self.sq is not None:
                     torch_ref.update_adam(
                         self.model.params, self.model.grads, self.vel,
                         self.sq, c.dt, scale, c.beta1, c.beta2, c.adam_eps,
-                        c.weight_decay, self.opt_step)
+                        c.weight_decay, self._opt_step)
                 elif self.vel is not None:
                     torch_ref.update_momentum(
                         self.model.params, self.model.grads, self.vel, c.dt,

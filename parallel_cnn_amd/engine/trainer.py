@@ -73,6 +73,7 @@ class Trainer:
         self.ctx = ctx or pdist.DistContext()
         self.device = torch.device(cfg.resolved_device())
         self.backend = cfg.resolved_backend()
+        cfg.loss_scaling()      # validates; refuses loss scaling for lenet5
         if self.backend == "hip" and self.device.type != "cuda":
             raise RuntimeError("hip backend requires a GPU device")
         if self.backend in ("hip", "cpu"):

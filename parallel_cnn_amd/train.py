@@ -82,6 +82,10 @@ def main(argv=None) -> int:
     total = time.perf_counter() - t0
     if ctx.is_main:
         print(f"\n Time - {total * 1e3:f} ms", flush=True)
+    ls = getattr(trainer, "loss_scale_state", lambda: None)()
+    if ls is not None and ctx.is_main:
+        print(f"loss scale: {ls['scale']:g}, updates applied: "
+              f"{ls['t'] - 1}, steps skipped: {ls['skipped']}", flush=True)
 
     if cfg.ckpt_save and ctx.is_main:
         from .utils.checkpoint import save_checkpoint

@@ -4,7 +4,9 @@ epoch cursor, host/device RNG states — so train(2N epochs) ==
 train(N) -> save -> load -> train(N)).  A non-default optimizer (momentum
 or weight decay) adds its velocity as flat LE fp32 at `path + '.vel'`; Adam
 puts its first moment there, its second moment at `path + '.sq'` and its
-update count in the sidecar."""
+update count in the sidecar.  A DeepCNN loss scaler adds its device state
+(`loss_scale`: scale, good_steps, skipped, t) to the sidecar; a sidecar
+without it resumes from the configured initial scale."""
 from __future__ import annotations
 
 import base64
@@ -66,6 +68,9 @@ def save_checkpoint(trainer, path: str) -> None:
         meta["momentum"] = trainer.cfg.momentum
         meta["weight_decay"] = trainer.cfg.weight_decay
         meta["nesterov"] = trainer.cfg.nesterov
+    ls = getattr(trainer, "loss_scale_state", lambda: None)()
+    if ls is not None:
+        meta["loss_scale"] = ls
     with open(path + ".meta.json", "w") as f:
         json.dump(meta, f, indent=1)
 
@@ -120,6 +125,19 @@ def _load_adam_state(trainer, path: str, meta: Optional[dict]) -> None:
     trainer.opt_step = int(meta["opt_step"])
 
 
+def _load_loss_scaler(trainer, meta: Optional[dict]) -> None:
+    """Restore the device loss scaler from the sidecar's `loss_scale`.  A
+    sidecar without it (or none) leaves the scaler at the configured initial
+    scale, with the update count the optimizer state above gave it."""
+    if getattr(trainer, "ls_state", None) is None:
+        return
+    ls = (meta or {}).get("loss_scale")
+    if ls is None:
+        return
+    trainer.set_loss_scale_state(float(ls["scale"]), int(ls["good_steps"]),
+                                 int(ls["skipped"]), int(ls["t"]))
+
+
 def load_checkpoint(trainer, path: str) -> Optional[dict]:
     """Loads weights; restores global_step/epoch/RNG from the sidecar if
     present.  Returns the metadata dict (or None)."""
@@ -135,6 +153,7 @@ def load_checkpoint(trainer, path: str) -> Optional[dict]:
         _load_adam_state(trainer, path, meta)
     else:
         _load_velocity(trainer, path)
+    _load_loss_scaler(trainer, meta)
     if meta is None:
         return None
     if meta.get("n_params") not in (None, int(trainer.model.params.numel())):

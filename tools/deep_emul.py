@@ -46,8 +46,12 @@ def rounder(dtype):
     return r
 
 
-def hooks_for(act_dtype: str):
-    """(round_operand, round_store) emulating the hip path at act_dtype."""
+def hooks_for(act_dtype: str, loss_scale: float = 1.0):
+    """(round_operand, round_store) emulating the hip path at act_dtype.
+    Loss scaling changes what is stored, not how it is rounded: grads64 takes
+    the scale itself, and the hooks are the same at every loss_scale."""
+    if not loss_scale >= 1.0:
+        raise ValueError(f"loss_scale must be >= 1, got {loss_scale}")
     return rounder(torch.bfloat16), rounder(STORE_DTYPE[act_dtype])
 
 
@@ -74,9 +78,13 @@ def _im2col(x_nchw, st):
 
 
 def grads64(x_nhwc: torch.Tensor, labels: torch.Tensor, params: torch.Tensor,
-            spec, round_operand=identity, round_store=identity):
+            spec, round_operand=identity, round_store=identity,
+            loss_scale: float = 1.0):
     """Batch-SUM gradient of the flat parameter vector, float64, plus the
-    summed loss.  x_nhwc [B,H,W,Cin], params: the fp32 master parameters."""
+    summed loss.  x_nhwc [B,H,W,Cin], params: the fp32 master parameters.
+    loss_scale: dz is multiplied by it ahead of dflat (where k_fc_fwd does),
+    every stored backward tensor is rounded at the scaled magnitude, and the
+    gradient is divided by it before it is returned; the loss is unscaled."""
     ro, rs = round_operand, round_store
     p = params.detach().cpu().to(torch.float64)
     B = x_nhwc.shape[0]
@@ -109,6 +117,7 @@ def grads64(x_nhwc: torch.Tensor, labels: torch.Tensor, params: torch.Tensor,
     dz = F.one_hot(labels.to(torch.int64), spec.n_classes).to(
         torch.float64) - y
     loss = dz.norm(dim=1).sum().item()
+    dz = dz * loss_scale
     gv("fc_w").add_(torch.einsum("bk,bm->km", dz, flat).reshape(-1))
     gv("fc_b").add_(dz.sum(0))
     dflat = rs((dz @ fw) * flat * (1 - flat))
@@ -140,6 +149,8 @@ def grads64(x_nhwc: torch.Tensor, labels: torch.Tensor, params: torch.Tensor,
                         (st.h, st.w), st.k, padding=st.pad)
             pprev = pouts[i - 1]
             dppre = rs(dx * pprev * (1 - pprev))
+    if loss_scale != 1.0:
+        g /= loss_scale
     return g, loss
 
 
@@ -155,11 +166,14 @@ def block_ratios(got: torch.Tensor, want: torch.Tensor, spec):
     return out
 
 
-def oracle_pair(x_nhwc, labels, params, spec, act_dtype: str):
-    """(g_exact, loss_exact, emulated ratio per block) for one batch."""
+def oracle_pair(x_nhwc, labels, params, spec, act_dtype: str,
+                loss_scale: float = 1.0):
+    """(g_exact, loss_exact, emulated ratio per block) for one batch; the
+    emulation runs at loss_scale, the exact chain rule needs none."""
     g_exact, loss = grads64(x_nhwc, labels, params, spec)
-    ro, rs = hooks_for(act_dtype)
-    g_emul, _ = grads64(x_nhwc, labels, params, spec, ro, rs)
+    ro, rs = hooks_for(act_dtype, loss_scale)
+    g_emul, _ = grads64(x_nhwc, labels, params, spec, ro, rs,
+                        loss_scale=loss_scale)
     return g_exact, loss, block_ratios(g_emul, g_exact, spec)
 
 
