@@ -251,6 +251,12 @@ enum {
 // all cross-thread a1 LDS traffic: the kernel has 3 barriers total
 // ({stage} {conv+pool} {fc+residual} {fc-bwd + pool-bwd + loss}).
 //
+// Every multiply-add of the forward is an explicit fma, in a fixed order.
+// Left as `acc += w * x` the compiler chose a different mix of fused and
+// unfused operations per instantiation, and y in eval and infer mode
+// differed from y in train mode in the last bit.  With the fmas the forward
+// is the same arithmetic in every MODE and in k_fwdbwd_pair.
+//
 // INBLOCK (MODE_TRAIN only) is the first kernel of the in-block weight-grad
 // step: the conv and pool weight gradients of this image are formed from
 // the registers that already hold dz1, a1 and the input window, reduced
@@ -315,13 +321,13 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
         for (int u = 0; u < C1_K; ++u)
 #pragma unroll
           for (int v = 0; v < C1_K; ++v)
-            acc += w[u * C1_K + v] * xw[i + u][j + v];
+            acc = __builtin_fmaf(w[u * C1_K + v], xw[i + u][j + v], acc);
         const float av = sigmoidf_dev(acc);
         a1v[i * S1_K + j] = av;
         if (pool_mode == 1)
           pacc = fmaxf(pacc, av);
         else
-          pacc += params[OFF_S1W + i * S1_K + j] * av;
+          pacc = __builtin_fmaf(params[OFF_S1W + i * S1_K + j], av, pacc);
       }
     }
     if (MODE == MODE_TRAIN && !INBLOCK) {
@@ -351,7 +357,7 @@ __global__ __launch_bounds__(256) void k_fwdbwd(
 #pragma unroll
     for (int u = 0; u < (FC_IN + 15) / 16; ++u) {
       const int m = l + u * 16;
-      if (m < FC_IN) p += wk[m] * L.a2s[m];
+      if (m < FC_IN) p = __builtin_fmaf(wk[m], L.a2s[m], p);
     }
 #pragma unroll
     for (int off = 8; off > 0; off >>= 1) p += __shfl_down(p, off, 16);

@@ -1,11 +1,16 @@
 """GPU (MI355X) tests: every HIP kernel against the fp32 PyTorch/native-CPU
 oracle, end-to-end step parity, convergence, and the bench path."""
 import json
+import os
 import subprocess
 import sys
 
 import pytest
 import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                                os.pardir, "tools"))
+import lenet_emul  # noqa: E402  (tools/: the per-block rule)
 
 from parallel_cnn_amd import _C
 from parallel_cnn_amd.config import TrainConfig
@@ -74,6 +79,10 @@ def test_fwdbwd_wgrad_fp32_matches_oracle(B, device):
         tol = 2e-4 * max(1.0, b.abs().max().item()) if n == "grads" else 2e-4
         assert diff < tol, f"{n}: max abs diff {diff}"
     assert abs(got[7] - want[7]) < 1e-2 * max(1.0, abs(want[7]))
+    fails = lenet_emul.check_batch_gradient(
+        f"fwdbwd+wgrad fp32 B{B}", got[6], x, labels, params, "trainable",
+        "residual", "three_launch", "fp32")
+    assert not fails, fails
 
 
 @pytest.mark.parametrize("B", [64])
@@ -92,6 +101,10 @@ def test_fwdbwd_wgrad_bf16_acts_close(B, device):
     gdiff = (got[6] - want[6]).abs().max().item()
     gref = want[6].abs().max().item()
     assert gdiff < 2e-2 * max(1.0, gref), f"grads: {gdiff} vs max {gref}"
+    fails = lenet_emul.check_batch_gradient(
+        f"fwdbwd+wgrad bf16 B{B}", got[6], x, labels, params, "trainable",
+        "residual", "three_launch", "bf16")
+    assert not fails, fails
 
 
 def test_update_kernel(device):
@@ -221,6 +234,10 @@ def test_fwdbwd_wgrad_fp16_acts_close(device):
         assert diff < 1e-2, f"{n}: max abs diff {diff}"
     gdiff = (got[6] - want[6]).abs().max().item()
     assert gdiff < 1e-2 * max(1.0, want[6].abs().max().item()), gdiff
+    fails = lenet_emul.check_batch_gradient(
+        f"fwdbwd+wgrad fp16 B{B}", got[6], x, labels, params, "trainable",
+        "residual", "three_launch", "fp16")
+    assert not fails, fails
 
 
 @pytest.mark.parametrize("overlap", [False, True])

@@ -9,8 +9,15 @@ a user would, and driven through Trainer.step so the new binding runs:
   * bf16 activation storage;
   * uneven block arrival (a busy device) against the same run done quiet.
 """
+import os
+import sys
+
 import pytest
 import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                                os.pardir, "tools"))
+import lenet_emul  # noqa: E402  (tools/: the per-block rule)
 
 from parallel_cnn_amd.config import TrainConfig
 from parallel_cnn_amd.data.mnist import synthetic_mnist
@@ -73,6 +80,11 @@ def one_step_vs_oracle(monkeypatch, variant, B, act_dtype, gtol, pool,
     print(f"variant {variant} B {B} {act_dtype} {pool}/{loss}: "
           f"param diff {diff:.3e} tol {tol:.3e} |g|max {gmax:.3e}")
     assert diff < tol, f"params: max abs diff {diff} (tol {tol})"
+    fails = lenet_emul.check_step(
+        f"variant {variant} B{B} {act_dtype} {pool}/{loss}", params,
+        t.model.params.cpu(), t.cfg.dt, x, labels, pool, loss, "inblock",
+        act_dtype)
+    assert not fails, fails
     # the step must have moved the parameters by the oracle's amount
     assert (got - params.double()).abs().max().item() > 0.5 * step * gmax
     return t, y, ref_loss

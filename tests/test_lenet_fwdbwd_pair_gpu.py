@@ -3,16 +3,14 @@ in-block weight-grad LeNet step (PCNN_LENET_FWDBWD=pair).
 
 The pair kernel keeps the cell kernel's term order in every conv output, in
 the pool pre-activation (lane 0's running sum is handed to lane 1, which
-continues it), in the fc dot products and in the residual.  It is still not
-bit-identical to the cell kernel in a2, y and dz: the pair kernel fuses
-every multiply-add (explicit fma), while the cell kernel's `acc += w * x`
-is compiled to a mix of fused FMAs and unfused packed multiplies + adds (64
-v_pk_mul_f32 and 145 v_add_f32 in its forward phase), a mix that only the
-compiler defines.  Measured: a2 differs by one ulp (5.96e-08).  a2, y and dz
-are therefore held to the 1e-6 bound that applies when the forward is not
-bit-identical.  The slab rows differ in summation order as well: two
-200-term partials per cell added pairwise, and owner sums over 18 + 18
-(conv) or 8 x 27 (pool) rows instead of 36 or 4 x 54.
+continues it), in the fc dot products and in the residual, and both kernels
+now fuse every forward multiply-add explicitly.  When this file was written
+the cell kernel's `acc += w * x` was compiled to a compiler-chosen mix of
+fused FMAs and unfused packed multiplies + adds, and a2 differed by one ulp
+(5.96e-08); a2, y and dz are therefore still held to the 1e-6 bound that
+applies when the forward is not bit-identical.  The slab rows differ in
+summation order as well: two 200-term partials per cell added pairwise, and
+owner sums over 18 + 18 (conv) or 8 x 27 (pool) rows instead of 36 or 4 x 54.
 
   * the slab rows, a2 and dz against the per-image torch_ref oracle;
   * pair against cell through the direct launcher;
@@ -24,8 +22,15 @@ bit-identical.  The slab rows differ in summation order as well: two
 Every test runs with the knob set to `pair` (direct launcher calls pass
 variant=1, which is what the knob selects).
 """
+import os
+import sys
+
 import pytest
 import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                                os.pardir, "tools"))
+import lenet_emul  # noqa: E402  (tools/: the per-block rule)
 
 from parallel_cnn_amd.config import TrainConfig
 from parallel_cnn_amd.data.mnist import synthetic_mnist
@@ -108,11 +113,14 @@ def test_slab_rows_match_per_image_oracle(pool, loss, device, monkeypatch):
         tol = 2e-4 * max(1.0, gmax)
         print(f"{pool}/{loss} image {b}: slab diff {diff:.3e} tol {tol:.3e}")
         assert diff < tol, f"image {b}: max abs diff {diff} (tol {tol})"
-        assert want[:S.OFF_S1W].abs().max().item() > 0
+        assert got[b][:S.OFF_S1W].abs().max().item() > 0
         assert (dz[b] - dzr[0]).abs().max().item() < 2e-4
         assert (a2[b] - a2r.reshape(-1)).abs().max().item() < 2e-4
     if pool == "max":
         assert torch.count_nonzero(got[:, S.OFF_S1W:]).item() == 0
+    fails = lenet_emul.check_slab_rows(f"pair {pool}/{loss}", got, x, labels,
+                                       params, pool, loss, "fp32")
+    assert not fails, fails
 
 
 # ---------------------------------------------------------- pair vs cell
@@ -170,6 +178,10 @@ def test_one_step_matches_oracle(act_dtype, gtol, device, monkeypatch):
     print(f"pair B {B} {act_dtype}: param diff {diff:.3e} tol {tol:.3e} "
           f"|g|max {gmax:.3e}")
     assert diff < tol, f"params: max abs diff {diff} (tol {tol})"
+    fails = lenet_emul.check_step(
+        f"pair B{B} {act_dtype}", params, t.model.params.cpu(), t.cfg.dt, x,
+        labels, "trainable", "residual", "inblock", act_dtype)
+    assert not fails, fails
     assert (got - params.double()).abs().max().item() > 0.5 * step * gmax
     assert_clean_state(t)
     loss, n = t.consume_loss()

@@ -17,8 +17,15 @@ per-image block and stored as one slab row per image, then k_reduce_update
 The slab kernel is called through its binding and never reads the knob, so
 its cases are not parametrised over it.
 """
+import os
+import sys
+
 import pytest
 import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                                os.pardir, "tools"))
+import lenet_emul  # noqa: E402  (tools/: the per-block rule)
 
 from parallel_cnn_amd.config import TrainConfig
 from parallel_cnn_amd.data.mnist import synthetic_mnist
@@ -93,12 +100,15 @@ def test_slab_rows_match_per_image_oracle(pool, loss, device):
         tol = 2e-4 * max(1.0, gmax)
         print(f"{pool}/{loss} image {b}: slab diff {diff:.3e} tol {tol:.3e}")
         assert diff < tol, f"image {b}: max abs diff {diff} (tol {tol})"
-        assert want[:S.OFF_S1W].abs().max().item() > 0
+        assert got[b][:S.OFF_S1W].abs().max().item() > 0
         # the stores kernel 2 depends on are still made
         assert (dz[b].cpu() - dzr[0]).abs().max().item() < 2e-4
         assert (a2[b].cpu() - a2r.reshape(-1)).abs().max().item() < 2e-4
     if pool == "max":
         assert torch.count_nonzero(got[:, S.OFF_S1W:]).item() == 0
+    fails = lenet_emul.check_slab_rows(f"{pool}/{loss}", got, x, labels,
+                                       params, pool, loss, "fp32")
+    assert not fails, fails
 
 
 # -------------------------------------------------------------- one step
@@ -124,6 +134,11 @@ def one_step_vs_oracle(monkeypatch, knob, B, act_dtype, gtol, pool, loss):
     print(f"{knob} B {B} {act_dtype} {pool}/{loss}: param diff {diff:.3e} "
           f"tol {tol:.3e} |g|max {gmax:.3e}")
     assert diff < tol, f"params: max abs diff {diff} (tol {tol})"
+    fails = lenet_emul.check_step(
+        f"{knob} B{B} {act_dtype} {pool}/{loss}", params,
+        t.model.params.cpu(), t.cfg.dt, x, labels, pool, loss, knob,
+        act_dtype)
+    assert not fails, fails
     assert (got - params.double()).abs().max().item() > 0.5 * step * gmax
     if pool == "max":  # the pool parameters come out unchanged
         assert torch.equal(t.model.params[S.OFF_S1W:S.OFF_FW].cpu(),
